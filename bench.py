@@ -21,8 +21,22 @@ N = 8, so the message split stays its default).
 
 Prints ONE JSON line (rank 0) with the driver's fields plus "roofline" (dominant kernel:
 SURVEY.md 8(d)'s algorithmic bytes B_r of the rounds it consumes / its HIP-event time; the
-engine's own per-kernel byte model beside it as frac_engine_model) and "cpu_baseline" (two CPU
-legs on the host cores: the C/OpenMP oracle and the 1-core object-level relay simulator).
+engine's own per-kernel byte model beside it as frac_engine_model).
+
+A plain run does only what that line's headline needs: graph, warmup, the timed steps, the
+outputs of --dump-outputs, the line.  --full adds what takes runs of its own: one more step with
+every kernel class bracketed by HIP events ("kernel_ms_per_step", "kernel_time_frac_of_step"), one
+broadcast stepped round by round ("dominant_ms_by_round", "dominant_round_fracs",
+"roofline.survey_rounds_over_peak") and "cpu_baseline" (two CPU legs on the host cores: the
+C/OpenMP oracle and the 1-core object-level relay simulator; --no-cpu-baseline leaves it out).
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0's view):
+DIR/rounds.npy (float64 [rounds, len(ROUND_FIELDS)]: the per-round counters of run(), all below
+2^53) and, where the engine is a GraphNetwork, a fixed seeded sample of the seen plane it leaves
+behind: DIR/seen_peers.npy and DIR/seen_words.npy (float64: the sampled peer ids and word indices)
+and DIR/seen_sample.npy (float64 [words, peers, 2]: the low and high 32 bits of each sampled
+uint64 word).  Graph, origins and Philox seeds are fixed, so two builds given the same arguments
+can be compared file for file.
 """
 import argparse
 import json
@@ -49,6 +63,11 @@ WORKLOADS = {
                     "per-round edge-drop churn p=0.05, vertex-partitioned"),
 }
 GOSSIP_SEED, CHURN_SEED = 0x5EED, 0xC0FFEE
+# --dump-outputs: the counters of a RoundStats that are results (push_form is how the engine
+# scheduled the round, not one), and the seen-plane sample (2 * 8 B per sampled word: 32 MB)
+ROUND_FIELDS = ("round", "active", "new_deliveries", "relays", "active_vertices", "active_words",
+                "wedges", "deg_active", "scatter_words", "touched_words", "received", "received_exact")
+DUMP_SEED, DUMP_PEERS, DUMP_WORDS = 0xD0C5, 500_000, 4
 
 KCLASS = ("seed", "flood_pull", "gossip_scatter_atomic", "record", "gossip_update", "gossip_pull",
           "gossip_scatter_store", "gossip_fused")
@@ -241,6 +260,29 @@ def load_traffic(workload, kernel):
     return d.get("kernels", {}).get(kernel, {}).get("bytes_per_launch")
 
 
+def dump_outputs(path, net, rounds):
+    """The last timed step's results as float64 .npy files under `path` (module docstring)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    tab = np.array([[getattr(r, f) for f in ROUND_FIELDS] for r in rounds], dtype=np.float64)
+    np.save(os.path.join(path, "rounds.npy"), tab.reshape(len(rounds), len(ROUND_FIELDS)))
+    if not hasattr(net, "seen_word"):
+        return  # a vertex-partitioned rank holds its own peers' rows only: the counters stand for it
+    rng = np.random.default_rng(DUMP_SEED)
+    V, W = net.graph.V, net.W
+    peers = np.sort(rng.choice(V, size=min(V, DUMP_PEERS), replace=False))
+    # the first and the last word, and seeded ones between them
+    words = np.unique(np.concatenate([[0, W - 1], rng.choice(W, size=min(W, DUMP_WORDS - 2), replace=False)]))
+    sample = np.empty((len(words), len(peers), 2), dtype=np.float64)
+    for i, w in enumerate(words):
+        col = net.seen_word(int(w))[peers]
+        sample[i, :, 0] = (col & np.uint64(0xFFFFFFFF)).astype(np.float64)
+        sample[i, :, 1] = (col >> np.uint64(32)).astype(np.float64)
+    np.save(os.path.join(path, "seen_peers.npy"), peers.astype(np.float64))
+    np.save(os.path.join(path, "seen_words.npy"), words.astype(np.float64))
+    np.save(os.path.join(path, "seen_sample.npy"), sample)
+
+
 def launch_ranks(n, argv):
     """`bench.py --gpus N` started without a launcher (WORLD_SIZE unset, N > 1): run the N ranks
     as children of this process under torch.distributed.run (127.0.0.1 rendezvous) and return
@@ -266,6 +308,11 @@ def main():
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
     ap.add_argument("--cpu-sample-msgs", type=int, default=64)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: every kernel class's device time, the "
+                         "dominant kernel round by round, the CPU baseline (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (module docstring)")
     ap.add_argument("--peers", type=int, default=0, help="override the workload's peer count "
                     "(rehearsals only; the reported workload names the size actually run)")
     ap.add_argument("--msgs", type=int, default=0, help="override the workload's broadcast count "
@@ -279,6 +326,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit(f"--gpus {args.gpus}: need at least one rank")
+    if args.steps < 1:
+        raise SystemExit(f"--steps {args.steps}: need at least one timed step")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
 
@@ -352,7 +401,7 @@ def main():
         net.run()
     # the timed region brackets only the dominant kernel class with HIP events (on the engine's
     # stream): two event records per launch cost ~2.7 us of stream time each, ~0.8 ms per c4
-    # step over ~300 launches; the other classes are timed in an untimed step afterwards
+    # step over ~300 launches; with --full the other classes are timed in an untimed step afterwards
     kt_w = net.kernel_times()
     dominant = max(KCLASS, key=lambda k: kt_w[k][0])
     if timing:
@@ -391,16 +440,20 @@ def main():
 
     last = all_rounds[-1]
     local_last = net.local_rounds if partitioned else last  # this rank's kernels' work
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, last)  # before anything below runs the engine again
     W_local = (len(src) + 63) // 64 if not partitioned else (M + 63) // 64
     mb = model_bytes(local_last, w["mode"], W_local)
     dom_ms, dom_n = kt[dominant]  # the last timed step's dominant launches (live HIP events)
-    # every class's device time: one more (untimed) step with all classes bracketed
-    net.set_timed_classes(None)
-    net.reset()
-    net.run()
-    kt_all = net.kernel_times()
-    if dist is not None:
-        dist.barrier()
+    kt_all = None
+    if args.full:
+        # every class's device time: one more (untimed) step with all classes bracketed
+        net.set_timed_classes(None)
+        net.reset()
+        net.run()
+        kt_all = net.kernel_times()
+        if dist is not None:
+            dist.barrier()
     traffic = load_traffic(args.workload, dominant)
     sb_step = survey_bytes(local_last, w["mode"])
     sb_dom = survey_bytes_kernel(local_last, w["mode"], dominant)
@@ -409,14 +462,14 @@ def main():
     # per-kernel byte model is reported beside it
     achieved = sb_dom / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
     achieved_engine = mb[dominant] / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-    kernel_ms_total = sum(v[0] for v in kt_all.values())
+    kernel_ms_total = sum(v[0] for v in kt_all.values()) if kt_all is not None else None
     # per-round honesty: the SURVEY model charges 8 B per BIT relay, which in the peak gossip
     # rounds implies more than the HBM peak -- those rounds are listed, not averaged away; the
     # engine model (8 B per packed E word) and the PMC counter bytes stay physically bounded
     sb_rounds = survey_bytes_kernel(local_last, w["mode"], dominant, per_round=True)
     mb_rounds = [x[dominant] for x in model_bytes(local_last, w["mode"], W_local, per_round=True)]
     by_round = None
-    if w["mode"] == "gossip" and world == 1:
+    if args.full and w["mode"] == "gossip" and world == 1:
         # untimed: one more broadcast stepped round by round, the dominant kernel's device time
         # per round (a change of the dense-round schedule cannot pass for kernel speed); stepping
         # stores every round's frontier, which p2pg_run skips where nobody reads it
@@ -484,17 +537,18 @@ def main():
                                         if round_fracs is not None else None),
         },
         "timing_mode": ("HIP events around the dominant kernel class only inside the timed region "
-                        "(p2pg_set_timed_classes); kernel_ms_per_step from one untimed step with every "
-                        "class bracketed (round 5 on; earlier rounds bracketed every class)"),
+                        "(p2pg_set_timed_classes); kernel_ms_per_step (--full) from one untimed step with "
+                        "every class bracketed (round 5 on; earlier rounds bracketed every class)"),
         "dominant_round_fracs": round_fracs,
-        # (an untimed step after the timed region, every class bracketed by events)
-        "kernel_ms_per_step": {k: v[0] for k, v in kt_all.items()},
+        # (--full: an untimed step after the timed region, every class bracketed by events)
+        "kernel_ms_per_step": {k: v[0] for k, v in kt_all.items()} if kt_all is not None else None,
         "dominant_ms_by_round": by_round,
         "model_bytes_per_step": mb,
         "whole_step_model_GBps": sum(mb.values()) / (elapsed / args.steps) / 1e9,
         "survey_model_bytes_per_step": sb_step,
         "whole_step_frac_survey_model": sb_step / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBPS,
-        "kernel_time_frac_of_step": kernel_ms_total / (elapsed / args.steps * 1e3),
+        "kernel_time_frac_of_step": (kernel_ms_total / (elapsed / args.steps * 1e3)
+                                     if kernel_ms_total is not None else None),
         "relays_per_step": relays // args.steps,
         # arrivals (sum of message_count_recv, nodeconnection.py:215): relays less churn losses;
         # a churn run counts its losses only with count_received (a counting pass per round,
@@ -508,7 +562,7 @@ def main():
         if partitioned else None,
         "graph_gen_s": t_gen,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(g, w, src, args.cpu_sample_msgs, thr)
     net.close()
     if rank == 0:

@@ -68,6 +68,32 @@ def test_bench_gpus2_spawns_two_ranks():
 
 
 @pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the headline fields and leaves out what --full measures; --dump-outputs
+    writes the last timed step's results: config 2's 64 floods reach all 1000 peers (every sampled
+    seen word is all ones) with 448,064 relays, in 2 timed steps as asked."""
+    import numpy as np
+    p = _bench(["--gpus", "1", "--workload", "c2", "--steps", "2", "--warmup", "1",
+                "--dump-outputs", str(tmp_path / "out")], _env(), timeout=300)
+    assert p.returncode == 0, p.stderr[-4000:]
+    j = _json_line(p.stdout)
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["unit"] == "GTEPS" and j["dtype"] == "u64"
+    assert j["higher_is_better"] is True and j["relays_per_step"] == C2_RELAYS
+    assert j["value"] == pytest.approx(C2_RELAYS / (j["ms_per_step"] * 1e-3) / 1e9, rel=1e-9)
+    assert "cpu_baseline" not in j and j["kernel_ms_per_step"] is None
+    assert j["dominant_ms_by_round"] is None
+    got = {f: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert set(got) == {"rounds.npy", "seen_peers.npy", "seen_words.npy", "seen_sample.npy"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    rounds = got["rounds.npy"]
+    assert rounds.shape == (j["config"]["rounds"], 12)
+    assert rounds[:, 3].sum() == C2_RELAYS and rounds[:, 2].sum() == 64 * 1000  # relays, receipts
+    assert np.array_equal(got["seen_peers.npy"], np.arange(1000)) and got["seen_words.npy"].tolist() == [0.0]
+    assert got["seen_sample.npy"].shape == (1, 1000, 2)
+    assert (got["seen_sample.npy"] == float(0xFFFFFFFF)).all()
+
+
+@pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_bench_c5_partitioned_8_ranks_gloo():
     """Config 5's vertex-partitioned job at 8 ranks (gloo, all on cuda:0 of the one-GPU box) at
@@ -101,8 +127,9 @@ def test_bench_c4_vertex_split_4_ranks_gloo():
     one = _bench(["--gpus", "1", *common], _env(), timeout=300)
     assert one.returncode == 0, one.stderr[-4000:]
     j1 = _json_line(one.stdout)
-    four = _bench(["--gpus", "4", "--split", "vertex", "--dist-backend", "gloo", *common], _env(),
-                  timeout=600)
+    # --full: kernel_ms_per_step comes from a step of its own with every kernel class timed
+    four = _bench(["--gpus", "4", "--split", "vertex", "--dist-backend", "gloo", "--full", *common],
+                  _env(), timeout=600)
     assert four.returncode == 0, four.stderr[-4000:]
     j4 = _json_line(four.stdout)
     assert j4["n_gpus"] == 4

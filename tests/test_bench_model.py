@@ -86,6 +86,39 @@ def test_kernel_split_of_survey_bytes_is_a_partition(pattern):
         assert parts["gossip_update"] == whole
 
 
+def test_dump_outputs_sample_is_fixed_and_exact(tmp_path):
+    """--dump-outputs on a stand-in engine: float64 files, the same seeded sample on every call,
+    uint64 seen words recoverable from their 32-bit halves, at most 64 MB at any size."""
+    V, W = 700_000, 64
+
+    class Net:
+        graph = types.SimpleNamespace(V=V)
+
+        def seen_word(self, w):
+            return (np.arange(V, dtype=np.uint64) + np.uint64(w)) * np.uint64(0x9E3779B97F4A7C15)
+
+    Net.W = W
+    rounds = rounds_of(gossip_rounds(), [bench.ATOMIC] * 64)
+    for r in rounds:
+        r.round, r.active, r.received, r.received_exact = 0, 1, r.relays, 1
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), Net(), rounds)
+    a = {f: np.load(tmp_path / "a" / f) for f in ("rounds.npy", "seen_peers.npy", "seen_words.npy",
+                                                   "seen_sample.npy")}
+    for f, x in a.items():
+        assert x.dtype == np.float64 and np.array_equal(x, np.load(tmp_path / "b" / f))
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["rounds.npy"].shape == (len(rounds), len(bench.ROUND_FIELDS))
+    assert a["rounds.npy"][:, bench.ROUND_FIELDS.index("relays")].tolist() == [r.relays for r in rounds]
+    peers, words = a["seen_peers.npy"].astype(np.uint64), a["seen_words.npy"].astype(np.uint64)
+    assert len(peers) == bench.DUMP_PEERS and np.all(np.diff(a["seen_peers.npy"]) > 0)
+    assert words[0] == 0 and words[-1] == W - 1 and len(words) <= bench.DUMP_WORDS
+    s = a["seen_sample.npy"].astype(np.uint64)
+    for i, w in enumerate(words):
+        assert np.array_equal(s[i, :, 0] | (s[i, :, 1] << np.uint64(32)),
+                              (peers + w) * np.uint64(0x9E3779B97F4A7C15))
+
+
 def test_flood_models_agree():
     """Flood: the engine's pull model is SURVEY's B_r term for term."""
     ora = gossip_rounds()
