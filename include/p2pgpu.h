@@ -28,7 +28,11 @@
  *                                    first receipt (README.md:20: the app decides)
  *   p2pg_round_stats.received     <- sum over peers of message_count_recv (nodeconnection.py:215)
  *   p2pg_read_planes              <- each app's "seen" set + first-receipt (hop, sender)
- *   p2pg_last_error               <- (reference swallows errors via debug_print, node.py:80-83)
+ *   p2pg_message_reach / _tally   <- per broadcast: how many apps' "seen" sets hold it, and the
+ *                                    hops of the node_message events that put it there
+ *   p2pg_peer_counters            <- per peer: Node.message_count_send / message_count_recv
+ *                                    (node.py:65-67, :116; nodeconnection.py:215)
+ *   p2pg_last_error              <- (reference swallows errors via debug_print, node.py:80-83)
  *
  * Conventions: plain C types only; 0 = OK, negative = error (message via p2pg_last_error);
  * no exceptions cross the ABI; the engine owns all device memory; caller keeps ownership of
@@ -76,6 +80,14 @@ extern "C" {
                                     round's frontier after each round: config 5 +100 %); without
                                     it a churn run reports the sends of the round before there
                                     (an upper bound, received_exact = 0)                     */
+
+#define P2PG_FLAG_TALLY 32u /* run tallies on the device: per broadcast reach / hop sum / last
+                                    hop (p2pg_message_tally), per peer Node.message_count_send /
+                                    message_count_recv (p2pg_peer_counters).  2 V 8 + M 20 bytes of
+                                    device memory (config 4: 160 MB); every round keeps its whole
+                                    frontier rows, a column count follows each round and a per-peer
+                                    pass precedes the next (the price: DESIGN.md 4g).  Not on a
+                                    vertex-partitioned rank, not with snapshots                  */
 
 typedef struct p2pg_engine p2pg_engine;
 typedef struct p2pg_graph p2pg_graph;
@@ -186,6 +198,35 @@ int p2pg_read_planes(p2pg_engine* e, uint64_t* seen, int32_t* hop, int32_t* pare
 /* Word w of every peer's seen row (messages 64w .. 64w+63): out[V].  Full-size validation
  * without copying a whole plane (config 5: 51 GB at 100M peers x 4096 broadcasts).       */
 int p2pg_read_seen_word(p2pg_engine* e, int32_t w, uint64_t* out);
+/* ---- run tallies: what a p2pnetwork user reads off a finished run, computed on the device ----
+ * Per broadcast, the size of every peer's dedup "seen" set membership (README.md:20); per peer,
+ * the reference's only counters, Node.message_count_send / message_count_recv (node.py:65-67).
+ * All three: P2PG_ERR_STATE before p2pg_set_sources and between p2pg_step_begin / p2pg_step_end.
+ *
+ * Peers that hold message m now (column popcount of the seen plane), reach[M].  No flag
+ * needed, no cost to the rounds; valid between rounds on any engine with sources set,
+ * including after a p2pg_run that skipped frontier rows.  Not on a vertex-partitioned rank. */
+int p2pg_message_reach(p2pg_engine* e, uint64_t* reach);
+/* With P2PG_FLAG_TALLY, accumulated round by round from each round's first receipts -- the
+ * node_message events that pass dedup (node.py:334-338) -- (any pointer may be NULL):
+ *   reach[m]    first receipts of m so far, origin included (== p2pg_message_reach)
+ *   hop_sum[m]  sum over those receipts of their hop (round index); mean hop = hop_sum/reach
+ *   last_hop[m] round of m's latest first receipt (-1 before round 0 ran)
+ * Counted when the receipts happen: a later p2pg_drop_relays withdraws relays, not receipts. */
+int p2pg_message_tally(p2pg_engine* e, uint64_t* reach, uint64_t* hop_sum, int32_t* last_hop);
+/* With P2PG_FLAG_TALLY: sent[V], received[V] (either may be NULL).
+ *   sent[v]     send_to_node calls peer v made in the rounds run so far, lost ones included
+ *               (node.py:116 counts before sending), less relays withdrawn by
+ *               p2pg_drop_relays: Node.message_count_send.
+ *   received[v] those sends, from any peer, that are addressed to v and are not lost to
+ *               churn or to a connection p2pg_update_edges removed while they were in
+ *               flight: v's message_count_recv (nodeconnection.py:215) once the next round
+ *               has handed them over.  Exact under churn with or without P2PG_FLAG_RECEIVED.
+ * A round's sends are counted once they are final: when the next round starts, inside
+ * p2pg_update_edges, or by this call -- after which a p2pg_drop_relays or p2pg_update_edges at
+ * the same round boundary is refused (P2PG_ERR_STATE): read the counters after the changes of
+ * a boundary.  p2pg_reset and p2pg_set_sources zero all tallies. */
+int p2pg_peer_counters(p2pg_engine* e, uint64_t* sent, uint64_t* received);
 /* Summed device time per kernel class since the last reset (needs P2PG_FLAG_TIMING):
  * 0 seed (origination), 1 flood pull, 2 gossip scatter by row atomics (sparse rounds),
  * 3 record (validation), 4 gossip update (consume row atomics), 5 gossip pull (consume edge

@@ -189,6 +189,18 @@ struct p2pg_engine {
   uint64_t sent_last = 0, lost_last = 0;
   unsigned long long* d_cnt2 = nullptr;  // k_sends counters [2] (device) / pinned copy
   unsigned long long* h_cnt2 = nullptr;
+  // run tallies (P2PG_FLAG_TALLY; relay_tally.hip): per message reach / hop_sum [M] and last_hop
+  // [M], per peer sent / received [V], and the column count's shard scratch
+  unsigned long long* d_treach = nullptr;
+  unsigned long long* d_thop = nullptr;
+  int32_t* d_tlast = nullptr;
+  unsigned long long* d_tsent = nullptr;
+  unsigned long long* d_trecv = nullptr;
+  unsigned long long* d_tscratch = nullptr;
+  int32_t tally_pending = -1;   // the round whose sends the peer counters do not hold yet: they
+                                // are final (drops, removed connections) only at the next round's
+                                // start, in p2pg_update_edges or when the counters are read
+  int32_t tally_read_at = -1;   // e->round when p2pg_peer_counters took the pending round in
 };
 
 namespace {
@@ -220,6 +232,12 @@ void free_state(p2pg_engine* e) {
   dfree(e->d_cnt2);
   if (e->h_cnt2) (void)hipHostFree(e->h_cnt2);
   e->h_cnt2 = nullptr;
+  dfree(e->d_treach);
+  dfree(e->d_thop);
+  dfree(e->d_tlast);
+  dfree(e->d_tsent);
+  dfree(e->d_trecv);
+  dfree(e->d_tscratch);
   DevState& s = e->st;
   dfree(s.seen);
   if (e->seen_spare) {
@@ -564,6 +582,25 @@ bool count_lost_on(const p2pg_engine* e) {
 // Is the `received` counter exact (no churn, or churn losses counted)?
 bool received_exact(const p2pg_engine* e) { return e->cfg.churn_threshold == 0 || count_lost_on(e); }
 
+// Run tallies (P2PG_FLAG_TALLY): every round keeps its whole frontier rows, which the column
+// count (at the round's end) and the peer pass (before the next round) read.
+bool tally_on(const p2pg_engine* e) { return (e->cfg.flags & P2PG_FLAG_TALLY) != 0; }
+// Does a round of this engine need its frontier rows whole (no skipped / partial rows, no
+// batched decay rounds)?
+bool frontier_needed(const p2pg_engine* e) { return count_lost_on(e) || tally_on(e); }
+
+// Enqueue the peer counters of the pending round (its sends are final now): the sends leave on
+// gs (gone slots = connections removed while they were in flight), the round's own arrivals
+// travelled on graph_for_arrivals.  Stream order only, no host synchronisation.
+hipError_t flush_peer_tally(p2pg_engine* e, const DevGraph& gs) {
+  if (!tally_on(e) || e->tally_pending < 0) return hipSuccess;
+  const int32_t r = e->tally_pending;
+  e->tally_pending = -1;
+  RoundParams p = params(e);
+  p.round = r;
+  return launch_peer_tally(gs, graph_for_arrivals(e, r), e->st, p, e->d_tsent, e->d_trecv, e->stream);
+}
+
 // Enqueue the count of round r's lost sends (k_sends, count mode) over gs (the graph the sends
 // leave on; gone slots = removed connections) and gp (the graph round r's arrivals travelled
 // on: the senders' own first receipts); the count lands in h_cnt2[1] at the next stream sync.
@@ -658,6 +695,20 @@ int alloc_state(p2pg_engine* e) {
   if ((rc = A((void**)&s.stats, STAT_BYTES))) return rc;
   if ((rc = A((void**)&e->d_cnt2, 2 * sizeof(unsigned long long)))) return rc;
   HIPCHK(e, hipHostMalloc((void**)&e->h_cnt2, 2 * sizeof(unsigned long long)));
+  if (tally_on(e)) {  // 2 * V * 8 + M * 20 bytes, and the column count's shards (p2pg_reset zeroes)
+    const size_t sb = sizeof(unsigned long long) * (size_t)tally_scratch_words(e->W);
+    if ((rc = A((void**)&e->d_treach, sizeof(unsigned long long) * (size_t)e->M))) return rc;
+    if ((rc = A((void**)&e->d_thop, sizeof(unsigned long long) * (size_t)e->M))) return rc;
+    if ((rc = A((void**)&e->d_tlast, sizeof(int32_t) * (size_t)e->M))) return rc;
+    if ((rc = A((void**)&e->d_tsent, sizeof(unsigned long long) * (size_t)e->V))) return rc;
+    if ((rc = A((void**)&e->d_trecv, sizeof(unsigned long long) * (size_t)e->V))) return rc;
+    if ((rc = A((void**)&e->d_tscratch, sb))) return rc;
+    const hipError_t zr = hipMemsetAsync(e->d_tscratch, 0, sb, e->stream);
+    if (zr != hipSuccess) {
+      free_state(e);
+      return fail(e, P2PG_ERR_HIP, std::string("alloc_state (tallies): ") + hipGetErrorString(zr));
+    }
+  }
 #ifdef P2PG_PROF
   if ((rc = A((void**)&s.prof, sizeof(unsigned long long) * 16))) return rc;
   HIPCHK(e, hipMemset(s.prof, 0, sizeof(unsigned long long) * 16));
@@ -679,6 +730,9 @@ int p2pg_create(const p2pg_config* cfg, p2pg_engine** out) {
     return fail(nullptr, P2PG_ERR_ARG, "create: unknown mode");
   if (cfg->mode == P2PG_MODE_GOSSIP && (cfg->fanout < 1 || cfg->fanout > 16))
     return fail(nullptr, P2PG_ERR_ARG, "create: gossip fanout must be in [1, 16]");
+  if ((cfg->flags & P2PG_FLAG_TALLY) && (cfg->flags & P2PG_FLAG_LOCAL_GRAPH))
+    return fail(nullptr, P2PG_ERR_ARG, "create: P2PG_FLAG_TALLY is not available on a vertex-partitioned rank "
+                                       "(P2PG_FLAG_LOCAL_GRAPH): ghost rows would be counted on two ranks");
   int ndev = 0;
   hipError_t r = hipGetDeviceCount(&ndev);
   if (r != hipSuccess || ndev == 0)
@@ -1003,6 +1057,15 @@ int p2pg_reset(p2pg_engine* e) {
     HIPCHK(e, hipMemsetAsync(s.hop, 0xFF, (size_t)e->V * e->M * sizeof(int32_t), e->stream));
     HIPCHK(e, hipMemsetAsync(s.parent, 0xFF, (size_t)e->V * e->M * sizeof(int32_t), e->stream));
   }
+  if (tally_on(e)) {
+    HIPCHK(e, hipMemsetAsync(e->d_treach, 0, sizeof(unsigned long long) * (size_t)e->M, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->d_thop, 0, sizeof(unsigned long long) * (size_t)e->M, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->d_tlast, 0xFF, sizeof(int32_t) * (size_t)e->M, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->d_tsent, 0, sizeof(unsigned long long) * (size_t)e->V, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->d_trecv, 0, sizeof(unsigned long long) * (size_t)e->V, e->stream));
+  }
+  e->tally_pending = -1;
+  e->tally_read_at = -1;
   e->round = 0;
   e->done = false;
   e->failed.clear();
@@ -1056,6 +1119,10 @@ int p2pg_step_begin(p2pg_engine* e) {
   if (e->done) return P2PG_OK;
   HIPCHK(e, hipSetDevice(e->cfg.device));
   DevState& s = e->st;
+  {  // tallies: the last round's sends are final; its frontiers are overwritten from here on
+    const hipError_t x = flush_peer_tally(e, graph(e));
+    if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("step (peer counters): ") + hipGetErrorString(x));
+  }
   if (e->stats_clear) {
     HIPCHK(e, hipMemsetAsync(s.stats, 0, STAT_BYTES, e->stream));
     std::memset(e->stats_base, 0, sizeof(e->stats_base));
@@ -1088,7 +1155,10 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   if (!e->begun && (rc = p2pg_step_begin(e))) return rc;
   HIPCHK(e, hipSetDevice(e->cfg.device));
   DevState& s = e->st;
-  if (e->arr_round >= 0 && e->round > e->arr_round) free_arr(e);
+  if (e->arr_round >= 0 && e->round > e->arr_round) {
+    if (tally_on(e)) HIPCHK(e, hipStreamSynchronize(e->stream));  // (the peer pass queued above reads it)
+    free_arr(e);
+  }
   const DevGraph g = graph(e);
   RoundParams p = params(e);
   if (split_round(e)) {  // phase 0 ran in step_begin: the border peers now
@@ -1250,6 +1320,15 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     if (r != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("step (exchange pack): ") + hipGetErrorString(r));
     e->auto_round = e->round;
   }
+  if (tally_on(e)) {
+    // this round's first receipts per message: column counts of its frontier rows (whole on a
+    // tally engine); its sends wait for the next boundary (flush_peer_tally)
+    const hipError_t x = launch_column_count(s.F[e->round & 1], s.A[e->round & 1], e->V, e->W, e->M, e->round,
+                                             e->d_tscratch, nullptr, e->d_treach, e->d_thop, e->d_tlast,
+                                             e->stream);
+    if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("step (message tallies): ") + hipGetErrorString(x));
+    e->tally_pending = e->round;
+  }
   const bool cnt_lost = count_lost_on(e);
   if (cnt_lost) {  // this round's lost sends: the next round's arrivals are its sends minus them
     hipError_t x = enqueue_lost_count(e, g, graph_for_arrivals(e, e->round), e->round);
@@ -1326,7 +1405,7 @@ constexpr int BATCH_MAX = 8;
 
 static bool decay_batchable(const p2pg_engine* e) {
   const int br = e->batch_rounds < 0 ? BATCH_MAX : e->batch_rounds;
-  return br > 1 && e->have_state && !e->done && !e->begun && e->round > 0 && !count_lost_on(e) &&
+  return br > 1 && e->have_state && !e->done && !e->begun && e->round > 0 && !frontier_needed(e) &&
          e->cfg.mode == P2PG_MODE_GOSSIP && e->saw_dense && !e->last_push_e &&
          e->last_new < e->prev2_new && e->prev_sw > 0 && !e->consume_next && e->arr_round < 0 &&
          !e->d_gid && !(e->cfg.flags & P2PG_FLAG_NO_AUTOSTOP) && e->push_mode != 2 &&
@@ -1452,7 +1531,7 @@ int p2pg_run(p2pg_engine* e, int32_t max_rounds, p2pg_round_stats* per_round,
     // only the last two rounds a call may run can leave frontiers behind for the caller (the
     // deliveries of the last round and their parents in the round before; snapshots); a
     // quiescent round has none
-    e->skip_frontier = n + 2 < max_rounds && !count_lost_on(e);  // (the lost count reads F)
+    e->skip_frontier = n + 2 < max_rounds && !frontier_needed(e);  // (the lost count / tallies read F)
     rc = p2pg_step(e, per_round ? &per_round[n] : &tmp);
     e->skip_frontier = false;
     if (rc < 0) return rc;
@@ -1608,6 +1687,9 @@ int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32
   if (!e || n < 0 || (n > 0 && (!peer || !msg))) return fail(e, P2PG_ERR_ARG, "drop_relays: bad arguments");
   int rc = sends_state(e, "drop_relays");
   if (rc) return rc;
+  if (tally_on(e) && e->tally_read_at == e->round)
+    return fail(e, P2PG_ERR_STATE, "drop_relays: p2pg_peer_counters has counted this round's sends already; "
+                                   "read the counters after the changes of a round boundary");
   if (n == 0) return P2PG_OK;
   if (e->d_gid || (e->cfg.flags & P2PG_FLAG_LOCAL_GRAPH))
     return fail(e, P2PG_ERR_STATE, "drop_relays: not on a vertex-partitioned rank");
@@ -1714,8 +1796,78 @@ int p2pg_read_seen_word(p2pg_engine* e, int32_t w, uint64_t* out) {
   return P2PG_OK;
 }
 
+// Shared preconditions of the tally reads: sources set, between rounds.
+static int tally_state(p2pg_engine* e, const char* what, bool need_flag) {
+  const std::string w(what);
+  if (!e) return fail(e, P2PG_ERR_ARG, w + ": no engine");
+  if (!e->have_state) return fail(e, P2PG_ERR_STATE, w + ": no sources set");
+  if (e->begun) return fail(e, P2PG_ERR_STATE, w + ": a round has begun (step_begin)");
+  if (need_flag && !tally_on(e)) return fail(e, P2PG_ERR_STATE, w + ": needs P2PG_FLAG_TALLY");
+  return P2PG_OK;
+}
+
+int p2pg_message_reach(p2pg_engine* e, uint64_t* reach) {
+  int rc = tally_state(e, "message_reach", false);
+  if (rc) return rc;
+  if (!reach) return fail(e, P2PG_ERR_ARG, "message_reach: no output array");
+  if (e->d_gid || (e->cfg.flags & P2PG_FLAG_LOCAL_GRAPH))
+    return fail(e, P2PG_ERR_STATE, "message_reach: not on a vertex-partitioned rank (ghost rows are "
+                                   "another rank's peers)");
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  // the shard scratch and the counts: the engine's own scratch with the flag, else for this call
+  const size_t sb = sizeof(unsigned long long) * (size_t)tally_scratch_words(e->W);
+  unsigned long long *scratch = e->d_tscratch, *out = nullptr;
+  hipError_t r = hipMalloc((void**)&out, sizeof(unsigned long long) * (size_t)e->M);
+  if (r == hipSuccess && !scratch) {
+    r = hipMalloc((void**)&scratch, sb);
+    if (r == hipSuccess) r = hipMemsetAsync(scratch, 0, sb, e->stream);
+  }
+  if (r == hipSuccess)
+    r = launch_column_count(e->st.seen, nullptr, e->V, e->W, e->M, 0, scratch, out, nullptr, nullptr, nullptr,
+                            e->stream);
+  if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+  if (r == hipSuccess) r = hipMemcpy(reach, out, sizeof(unsigned long long) * (size_t)e->M, hipMemcpyDeviceToHost);
+  if (scratch && scratch != e->d_tscratch) (void)hipFree(scratch);
+  if (out) (void)hipFree(out);
+  if (r != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("message_reach: ") + hipGetErrorString(r));
+  return P2PG_OK;
+}
+
+int p2pg_message_tally(p2pg_engine* e, uint64_t* reach, uint64_t* hop_sum, int32_t* last_hop) {
+  int rc = tally_state(e, "message_tally", true);
+  if (rc) return rc;
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  const size_t n = (size_t)e->M;
+  if (reach) HIPCHK(e, hipMemcpy(reach, e->d_treach, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+  if (hop_sum) HIPCHK(e, hipMemcpy(hop_sum, e->d_thop, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+  if (last_hop) HIPCHK(e, hipMemcpy(last_hop, e->d_tlast, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  return P2PG_OK;
+}
+
+int p2pg_peer_counters(p2pg_engine* e, uint64_t* sent, uint64_t* received) {
+  int rc = tally_state(e, "peer_counters", true);
+  if (rc) return rc;
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  if (e->tally_pending >= 0) {
+    // the last round's sends count as they stand: a later drop or topology update at this
+    // boundary would change sends already counted, so those calls refuse from here on
+    const hipError_t x = flush_peer_tally(e, graph(e));
+    if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("peer_counters: ") + hipGetErrorString(x));
+    e->tally_read_at = e->round;
+  }
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  const size_t n = (size_t)e->V;
+  if (sent) HIPCHK(e, hipMemcpy(sent, e->d_tsent, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+  if (received) HIPCHK(e, hipMemcpy(received, e->d_trecv, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+  return P2PG_OK;
+}
+
 int p2pg_set_global_ids(p2pg_engine* e, const int32_t* gid) {
   if (!e || !e->d_rowptr) return fail(e, P2PG_ERR_STATE, "set_global_ids: load a graph first");
+  if (tally_on(e))
+    return fail(e, P2PG_ERR_STATE, "set_global_ids: a P2PG_FLAG_TALLY engine cannot be a vertex-partitioned "
+                                   "rank (ghost rows would be counted on two ranks)");
   HIPCHK(e, hipSetDevice(e->cfg.device));
   dfree(e->d_gid);
   e->h_gid.clear();
@@ -1928,6 +2080,9 @@ int p2pg_update_edges(p2pg_engine* e, int64_t n_add, const int32_t* add, int64_t
   if (e->arr_round >= 0 && e->arr_round == e->round)
     return fail(e, P2PG_ERR_STATE, "update_edges: one update per round boundary");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "update_edges: a round has begun (step_begin)");
+  if (tally_on(e) && e->have_state && e->tally_read_at == e->round)
+    return fail(e, P2PG_ERR_STATE, "update_edges: p2pg_peer_counters has counted this round's sends already; "
+                                   "read the counters after the changes of a round boundary");
   const int64_t V = e->V;
   const std::vector<int64_t>& rp = e->h_rowptr;
   const std::vector<int32_t>& ci = e->h_colidx;
@@ -1999,7 +2154,19 @@ int p2pg_update_edges(p2pg_engine* e, int64_t n_add, const int32_t* add, int64_t
     for (const auto& d : dels) gone[slot_of(d.first, d.second)] = 1;
     uint8_t* d_gone = nullptr;
     HIPCHK(e, hipMalloc((void**)&d_gone, gone.empty() ? 1 : gone.size()));
-    if (!gone.empty()) HIPCHK(e, hipMemcpy(d_gone, gone.data(), gone.size(), hipMemcpyHostToDevice));
+    hipError_t gr = gone.empty() ? hipSuccess : hipMemcpy(d_gone, gone.data(), gone.size(), hipMemcpyHostToDevice);
+    if (gr == hipSuccess) {
+      // tallies: the last round's sends are final now -- the ones on removed connections are lost
+      DevGraph gs = graph(e);
+      gs.gone = d_gone;
+      gr = flush_peer_tally(e, gs);
+      // (it reads the arrival graph freed below)
+      if (gr == hipSuccess && tally_on(e)) gr = hipStreamSynchronize(e->stream);
+    }
+    if (gr != hipSuccess) {
+      (void)hipFree(d_gone);
+      return fail(e, P2PG_ERR_HIP, std::string("update_edges: ") + hipGetErrorString(gr));
+    }
     if (!dels.empty()) {
       // the arrivals of the next round lose the sends in flight on the removed connections: count
       // the last round's lost sends again with those slots gone (churn losses included), while the
@@ -2058,6 +2225,11 @@ int p2pg_update_edges(p2pg_engine* e, int64_t n_add, const int32_t* add, int64_t
     e->d_rowptr = nullptr;
     e->d_colidx = nullptr;
     e->arr_round = e->round;
+  } else if (tally_on(e) && e->tally_pending >= 0) {
+    // a finished run: its last round's sends (none pass a quiet round) over the graph they left on
+    hipError_t x = flush_peer_tally(e, graph(e));
+    if (x == hipSuccess) x = hipStreamSynchronize(e->stream);
+    if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("update_edges (peer counters): ") + hipGetErrorString(x));
   }
   std::vector<uint32_t> rev;
   if ((rc = check_csr(e, V, nrp.data(), nci.data(), rev))) return rc;
@@ -2148,6 +2320,8 @@ int p2pg_snapshot_size(p2pg_engine* e, int64_t* bytes) {
 int p2pg_snapshot(p2pg_engine* e, void* buf, int64_t cap) {
   if (!e || !buf) return fail(e, P2PG_ERR_ARG, "snapshot: bad arguments");
   if (!e->have_state) return fail(e, P2PG_ERR_STATE, "snapshot: no sources set");
+  if (tally_on(e))
+    return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold run tallies (P2PG_FLAG_TALLY)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "snapshot: a round has begun (step_begin)");
   if (e->arr_round >= 0 && e->arr_round == e->round)
     return fail(e, P2PG_ERR_STATE, "snapshot: take it before a topology update or after the next round");
@@ -2209,6 +2383,8 @@ int p2pg_snapshot(p2pg_engine* e, void* buf, int64_t cap) {
 int p2pg_restore(p2pg_engine* e, const void* buf, int64_t size) {
   if (!e || !buf || size < (int64_t)sizeof(SnapHeader)) return fail(e, P2PG_ERR_ARG, "restore: bad arguments");
   if (!e->have_state) return fail(e, P2PG_ERR_STATE, "restore: set the same sources first");
+  if (tally_on(e))
+    return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold run tallies (P2PG_FLAG_TALLY)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "restore: a round has begun (step_begin)");
   SnapHeader h;
   std::memcpy(&h, buf, sizeof(h));

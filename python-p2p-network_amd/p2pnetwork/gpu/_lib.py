@@ -20,6 +20,7 @@ FLAG_TIMING = 2
 FLAG_NO_AUTOSTOP = 4
 FLAG_LOCAL_GRAPH = 8
 FLAG_RECEIVED = 16
+FLAG_TALLY = 32
 
 # graph kinds of p2pg_graph_generate
 GRAPH_RANDOM_REGULAR = 0
@@ -94,6 +95,9 @@ SIGNATURES = {
     "p2pg_drop_relays": (ctypes.c_int, [_P, _I64, _P, _P]),
     "p2pg_read_planes": (ctypes.c_int, [_P, _P, _P, _P]),
     "p2pg_read_seen_word": (ctypes.c_int, [_P, _I32, _P]),
+    "p2pg_message_reach": (ctypes.c_int, [_P, _P]),
+    "p2pg_message_tally": (ctypes.c_int, [_P, _P, _P, _P]),
+    "p2pg_peer_counters": (ctypes.c_int, [_P, _P, _P]),
     "p2pg_kernel_times": (ctypes.c_int, [_P, _P, _P]),
     "p2pg_set_timed_classes": (ctypes.c_int, [_P, ctypes.c_uint32]),
     "p2pg_set_global_ids": (ctypes.c_int, [_P, _P]),

@@ -19,6 +19,7 @@ the C-ABI of include/p2pgpu.h.  The hook surface is kept in batched form: per ro
 subclasses is in ``p2pnetwork.gpu.compat``.
 """
 import ctypes
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
@@ -95,6 +96,14 @@ class Deliveries:
         return len(self.peer)
 
 
+# Run tallies (GraphNetwork(tally=True)): per broadcast, uint64 [M] reach (peers that received
+# it, origin included) and hop_sum (sum of their hops; mean hop = hop_sum / reach), int32 [M]
+# last_hop (round of the latest first receipt, -1 = none yet) -- p2pg_message_tally
+MessageTally = namedtuple("MessageTally", "reach hop_sum last_hop")
+# ... and per peer, uint64 [V]: Node.message_count_send (node.py:65, :116) and
+# message_count_recv (nodeconnection.py:215) -- p2pg_peer_counters
+PeerCounters = namedtuple("PeerCounters", "sent received")
+
 # index of SnapHeader.total_relays in the snapshot header viewed as uint64 words (engine.cpp:
 # magic 0, version/mode 1, V 2, nnz 3, M/W 4, fanout/round 5, flags/thr 6, base/done 7,
 # consume/has_next 8, gossip_seed 9, churn_seed 10, graph_hash 11, src_hash 12, total_relays 13)
@@ -120,7 +129,7 @@ class GraphNetwork:
     def __init__(self, graph, mode="flood", fanout=3, gossip_seed=0x5EED, churn=0.0,
                  churn_threshold_value=None, churn_seed=0xC0FFEE, record=False, timing=False,
                  device=0, msg_id_base=0, callback=None, autostop=True, local_graph=False,
-                 count_received=False):
+                 count_received=False, tally=False):
         if not isinstance(graph, PeerGraph):
             raise TypeError("graph must be a PeerGraph")
         if mode not in ("flood", "gossip"):
@@ -141,7 +150,8 @@ class GraphNetwork:
         cfg.flags = ((_lib.FLAG_RECORD if record else 0) | (_lib.FLAG_TIMING if timing else 0)
                      | (0 if autostop else _lib.FLAG_NO_AUTOSTOP)
                      | (_lib.FLAG_LOCAL_GRAPH if local_graph else 0)
-                     | (_lib.FLAG_RECEIVED if count_received else 0))
+                     | (_lib.FLAG_RECEIVED if count_received else 0)
+                     | (_lib.FLAG_TALLY if tally else 0))
         cfg.device = int(device)
         self.config = cfg
         L = _lib.lib()
@@ -375,6 +385,34 @@ class GraphNetwork:
         s = self.seen_plane()
         bits = np.unpackbits(s.view(np.uint8).reshape(self.graph.V, -1), axis=1, bitorder="little")
         return bits[:, :self.M].astype(bool)
+
+    # -- run tallies, computed on the device -------------------------------------------------
+    def message_reach(self):
+        """uint64 [M]: peers that hold each broadcast now -- the column counts of the seen plane,
+        without copying it (p2pg_message_reach; needs no flag)."""
+        out = np.zeros(self.M, dtype=np.uint64)
+        self._check(_lib.lib().p2pg_message_reach(self._h, _lib.ptr(out)))
+        return out
+
+    def message_tally(self):
+        """MessageTally(reach, hop_sum, last_hop) per broadcast, accumulated from every round's
+        first receipts; needs tally=True (p2pg_message_tally)."""
+        reach = np.zeros(self.M, dtype=np.uint64)
+        hop_sum = np.zeros(self.M, dtype=np.uint64)
+        last_hop = np.zeros(self.M, dtype=np.int32)
+        self._check(_lib.lib().p2pg_message_tally(self._h, _lib.ptr(reach), _lib.ptr(hop_sum),
+                                                  _lib.ptr(last_hop)))
+        return MessageTally(reach, hop_sum, last_hop)
+
+    def peer_counters(self):
+        """PeerCounters(sent, received) per peer: Node.message_count_send / message_count_recv of
+        the rounds run so far; needs tally=True.  Read them after a round boundary's drop_relays /
+        update_edges: those calls refuse once the boundary's sends are counted
+        (p2pg_peer_counters)."""
+        sent = np.zeros(self.graph.V, dtype=np.uint64)
+        received = np.zeros(self.graph.V, dtype=np.uint64)
+        self._check(_lib.lib().p2pg_peer_counters(self._h, _lib.ptr(sent), _lib.ptr(received)))
+        return PeerCounters(sent, received)
 
     def hop_parent(self):
         """(hop, parent) int32 [V, M]; needs record=True.  -1 = not delivered / origin."""
