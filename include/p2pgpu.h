@@ -12,6 +12,9 @@
  *                                    Node.all_nodes = nodes_inbound + nodes_outbound (node.py:75-78)
  *   p2pg_set_sources              <- the originating Node.send_to_nodes(data) call per broadcast
  *                                    (node.py:106-112)
+ *   p2pg_set_sources_at /         <- the same call made later in the run: an app says something
+ *   p2pg_originate                   whenever it has something to say (node.py:106-112), so each
+ *                                    broadcast has its own start round
  *   p2pg_step / p2pg_run          <- one / all rounds of: NodeConnection.run receive loop
  *                                    (nodeconnection.py:186-218) -> Node.node_message
  *                                    (node.py:334-338) -> app dedup -> send_to_nodes(data,
@@ -105,7 +108,8 @@ typedef struct p2pg_config {
 
 typedef struct p2pg_round_stats {
   int32_t round;             /* round index r (0 = origination)                           */
-  int32_t active;            /* 1 if messages are still in flight after this round        */
+  int32_t active;            /* 1 if messages are still in flight after this round, or a
+                                broadcast is scheduled to start in a later one            */
   uint64_t new_deliveries;   /* (peer,msg) first receipts in round r (= node_message events
                                 that pass dedup)                                          */
   uint64_t relays;           /* send_to_node calls made in round r (message_count_send)   */
@@ -154,7 +158,30 @@ int p2pg_churn_lost(uint32_t round, uint32_t a, uint32_t b, uint32_t threshold, 
 int p2pg_create(const p2pg_config* cfg, p2pg_engine** out);
 int p2pg_load_csr(p2pg_engine* e, int64_t V, const int64_t* rowptr, const int32_t* colidx);
 int p2pg_set_sources(p2pg_engine* e, int32_t M, const int32_t* src);
-/* Back to round 0 with the same graph and sources (clears seen/frontier state). */
+/* Broadcasts that enter the network over time (Node.send_to_nodes(data) called at the origin
+ * whenever the app has something to say, node.py:106-112): like p2pg_set_sources, and message m
+ * originates at src[m] in round start[m] >= 0 instead of round 0; start[m] = -1 with src[m] = -1
+ * declares an unscheduled message (it owns its bit column and does nothing until
+ * p2pg_originate schedules it).  In round r the arrivals are received first, then every m with
+ * start[m] == r originates: a first receipt of round r at the origin (hop r, parent -1) that
+ * sends to all deg connections (flood) or to the min(k, deg) Philox picks of (r, origin,
+ * msg_id_base + m) (gossip); those sends arrive in round r + 1 under round r's churn draw.
+ * Hops stay absolute round indices everywhere.  p2pg_round_stats.active stays 1 while a
+ * scheduled start lies ahead, so p2pg_run crosses idle gaps and stops after the last wave;
+ * unscheduled messages keep no run alive.  p2pg_reset keeps the schedule and replays it.
+ * start all zero is exactly p2pg_set_sources.  A gossip round with originations runs its
+ * receive pass and its pushes as separate passes (never P2PG_PUSH_FUSED / _UPDATE_EDGE).
+ * Not on a vertex-partitioned rank (P2PG_ERR_STATE); an engine whose schedule holds a start
+ * other than 0 refuses p2pg_snapshot / p2pg_restore (P2PG_ERR_STATE).                       */
+int p2pg_set_sources_at(p2pg_engine* e, int32_t M, const int32_t* src, const int32_t* start);
+/* Between rounds: schedule the unscheduled messages msg[i] to originate at peer[i] in `round`
+ * -- the send_to_nodes(data) an app decides on while it runs (node.py:106-112), e.g. a reply
+ * made in a batched node_message hook.  round >= max(1, the next round to run); every msg[i]
+ * in range, unscheduled and listed once; every peer[i] in range (P2PG_ERR_ARG otherwise,
+ * nothing changed).  Wakes an engine that had gone quiet.  P2PG_ERR_STATE between
+ * p2pg_step_begin / p2pg_step_end and on a vertex-partitioned rank.                        */
+int p2pg_originate(p2pg_engine* e, int64_t n, const int32_t* msg, const int32_t* peer, int32_t round);
+/* Back to round 0 with the same graph, sources and start rounds (clears seen/frontier state). */
 int p2pg_reset(p2pg_engine* e);
 /* One round. Returns 1 while messages are in flight, 0 when quiescent, < 0 on error. */
 int p2pg_step(p2pg_engine* e, p2pg_round_stats* out);
@@ -228,7 +255,7 @@ int p2pg_message_tally(p2pg_engine* e, uint64_t* reach, uint64_t* hop_sum, int32
  * a boundary.  p2pg_reset and p2pg_set_sources zero all tallies. */
 int p2pg_peer_counters(p2pg_engine* e, uint64_t* sent, uint64_t* received);
 /* Summed device time per kernel class since the last reset (needs P2PG_FLAG_TIMING):
- * 0 seed (origination), 1 flood pull, 2 gossip scatter by row atomics (sparse rounds),
+ * 0 seed (origination, in round 0 and later), 1 flood pull, 2 gossip scatter by row atomics (sparse rounds),
  * 3 record (validation), 4 gossip update (consume row atomics), 5 gossip pull (consume edge
  * stores), 6 gossip scatter by edge stores (dense rounds), 7 gossip fused pull + scatter
  * (a dense round after a dense round).                                                  */

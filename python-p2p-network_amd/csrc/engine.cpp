@@ -13,6 +13,9 @@
 //                  (sparse rounds), or E[r&1] per-connection masks (dense rounds; the next
 //                  round pulls them; a dense round after a dense round runs pull + scatter
 //                  as one fused pass, k_gossip_fused)
+//   r >= 1         originate: F[r&1], seen, A[r&1] |= the bits of the messages whose start round
+//                  is r, after the receive pass (relay_originate.hip); such a gossip round is
+//                  never fused: update / pull, originate, then the separate scatter
 //   record         hop/parent planes for the bits of F[r&1]   (P2PG_FLAG_RECORD only)
 #include <hip/hip_runtime.h>
 
@@ -201,6 +204,22 @@ struct p2pg_engine {
                                 // are final (drops, removed connections) only at the next round's
                                 // start, in p2pg_update_edges or when the counters are read
   int32_t tally_read_at = -1;   // e->round when p2pg_peer_counters took the pending round in
+  // Start rounds (p2pg_set_sources_at / p2pg_originate): h_start[m] = the round message m
+  // originates in at h_src[m] (0: round 0's seed; -1 with h_src[m] = -1: unscheduled).  The
+  // messages that start after round 0 are kept on the device sorted by (round, peer, msg) and cut
+  // into groups of one (round, peer) each (k_originate: one wave per group); sched_rounds holds
+  // the group range of every round that has any.  Uploaded when the schedule changes, not per round.
+  struct SchedRound {
+    int32_t round;
+    int64_t g_lo, g_hi;  // its groups
+  };
+  std::vector<int32_t> h_start;
+  std::vector<SchedRound> sched_rounds;  // ascending rounds
+  int32_t last_start = 0;        // the latest scheduled start round (0: nothing starts late)
+  bool late = false;             // some start is not 0 (a late or an unscheduled message)
+  int32_t* d_sched_peer = nullptr;
+  int32_t* d_sched_msg = nullptr;
+  int64_t* d_sched_grp = nullptr;
 };
 
 namespace {
@@ -275,6 +294,12 @@ void free_state(p2pg_engine* e) {
   dfree(s.prof);
 #endif
   dfree(e->d_src);
+  dfree(e->d_sched_peer);
+  dfree(e->d_sched_msg);
+  dfree(e->d_sched_grp);
+  e->sched_rounds.clear();
+  e->late = false;
+  e->last_start = 0;
   e->have_state = false;
 }
 
@@ -930,14 +955,105 @@ int p2pg_load_csr(p2pg_engine* e, int64_t V, const int64_t* rowptr, const int32_
   return P2PG_OK;
 }
 
-int p2pg_set_sources(p2pg_engine* e, int32_t M, const int32_t* src) {
-  if (!e || M <= 0 || !src) return fail(e, P2PG_ERR_ARG, "set_sources: need M > 0 and src");
-  if (!e->d_rowptr) return fail(e, P2PG_ERR_STATE, "set_sources: load a graph first");
-  for (int32_t m = 0; m < M; ++m)
-    if (src[m] < 0 || src[m] >= e->V) return fail(e, P2PG_ERR_ARG, "set_sources: source out of range");
+}  // extern "C"
+
+namespace {
+
+// The device schedule from h_src / h_start: the messages with start > 0 sorted by (round, peer,
+// msg), their (round, peer) groups, the group range of every round; d_src = round 0's seeds
+// (-1 for every other message).  Runs when the schedule changes (set_sources[_at], originate).
+int upload_schedule(p2pg_engine* e) {
+  const int32_t M = e->M;
+  std::vector<int32_t> seed0(M), order;
+  e->late = false;
+  e->last_start = 0;
+  for (int32_t m = 0; m < M; ++m) {
+    seed0[m] = e->h_start[m] == 0 ? e->h_src[m] : -1;
+    if (e->h_start[m] != 0) e->late = true;
+    if (e->h_start[m] > 0) {
+      order.push_back(m);
+      e->last_start = std::max(e->last_start, e->h_start[m]);
+    }
+  }
+  std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+    if (e->h_start[a] != e->h_start[b]) return e->h_start[a] < e->h_start[b];
+    return e->h_src[a] != e->h_src[b] ? e->h_src[a] < e->h_src[b] : a < b;
+  });
+  const size_t n = order.size();
+  std::vector<int32_t> peer(n), msg(n);
+  std::vector<int64_t> grp;
+  e->sched_rounds.clear();
+  for (size_t i = 0; i < n; ++i) {
+    const int32_t m = order[i];
+    peer[i] = e->h_src[m];
+    msg[i] = m;
+    const bool new_round = i == 0 || e->h_start[m] != e->h_start[order[i - 1]];
+    if (new_round || peer[i] != peer[i - 1]) {
+      if (new_round) {
+        if (!e->sched_rounds.empty()) e->sched_rounds.back().g_hi = (int64_t)grp.size();
+        e->sched_rounds.push_back({e->h_start[m], (int64_t)grp.size(), 0});
+      }
+      grp.push_back((int64_t)i);
+    }
+  }
+  if (!e->sched_rounds.empty()) e->sched_rounds.back().g_hi = (int64_t)grp.size();
+  grp.push_back((int64_t)n);
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  // (the stream may still run a round that reads the old arrays)
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipMemcpy(e->d_src, seed0.data(), sizeof(int32_t) * M, hipMemcpyHostToDevice));
+  dfree(e->d_sched_peer);
+  dfree(e->d_sched_msg);
+  dfree(e->d_sched_grp);
+  if (n) {
+    HIPCHK(e, hipMalloc((void**)&e->d_sched_peer, sizeof(int32_t) * n));
+    HIPCHK(e, hipMalloc((void**)&e->d_sched_msg, sizeof(int32_t) * n));
+    HIPCHK(e, hipMalloc((void**)&e->d_sched_grp, sizeof(int64_t) * grp.size()));
+    HIPCHK(e, hipMemcpy(e->d_sched_peer, peer.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->d_sched_msg, msg.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->d_sched_grp, grp.data(), sizeof(int64_t) * grp.size(), hipMemcpyHostToDevice));
+  }
+  return P2PG_OK;
+}
+
+// The originations of round r > 0, or nullptr.
+const p2pg_engine::SchedRound* sched_round(const p2pg_engine* e, int32_t r) {
+  if (r <= 0 || r > e->last_start) return nullptr;
+  auto it = std::lower_bound(e->sched_rounds.begin(), e->sched_rounds.end(), r,
+                             [](const p2pg_engine::SchedRound& a, int32_t x) { return a.round < x; });
+  return it != e->sched_rounds.end() && it->round == r ? &*it : nullptr;
+}
+
+// Does a scheduled start lie at or after round r?  (Unscheduled messages keep no run alive.)
+bool start_ahead(const p2pg_engine* e, int32_t r) { return e->last_start >= r && e->last_start > 0; }
+
+// Is this engine a rank of a vertex partition?
+bool partitioned(const p2pg_engine* e) { return e->d_gid || (e->cfg.flags & P2PG_FLAG_LOCAL_GRAPH); }
+
+// p2pg_set_sources (start == nullptr: every message starts in round 0) / p2pg_set_sources_at
+int set_sources(p2pg_engine* e, const char* what, int32_t M, const int32_t* src, const int32_t* start) {
+  const std::string w(what);
+  if (!e || M <= 0 || !src) return fail(e, P2PG_ERR_ARG, w + ": need M > 0 and src");
+  if (!e->d_rowptr) return fail(e, P2PG_ERR_STATE, w + ": load a graph first");
+  if (start && e->begun) return fail(e, P2PG_ERR_STATE, w + ": a round has begun (step_begin)");
+  bool late = false;
+  for (int32_t m = 0; m < M; ++m) {
+    const int32_t s = start ? start[m] : 0;
+    if (s < -1) return fail(e, P2PG_ERR_ARG, w + ": start round below -1");
+    if (s == -1 ? src[m] != -1 : (src[m] < 0 || src[m] >= e->V))
+      return fail(e, P2PG_ERR_ARG, s == -1 ? w + ": an unscheduled message (start -1) takes source -1"
+                                           : w + ": source out of range");
+    late |= s != 0;
+  }
+  if (late && partitioned(e))
+    return fail(e, P2PG_ERR_STATE, w + ": start rounds other than 0 are not available on a vertex-partitioned rank");
   HIPCHK(e, hipSetDevice(e->cfg.device));
   const int32_t W = (M + 63) / 64;
   e->h_src.assign(src, src + M);
+  if (start)
+    e->h_start.assign(start, start + M);
+  else
+    e->h_start.assign(M, 0);
   e->seed.ok = false;
   if (!e->have_state || W != e->W || M != e->M) {
     e->M = M;
@@ -945,8 +1061,53 @@ int p2pg_set_sources(p2pg_engine* e, int32_t M, const int32_t* src) {
     int rc = alloc_state(e);
     if (rc) return rc;
   }
-  HIPCHK(e, hipMemcpy(e->d_src, src, sizeof(int32_t) * M, hipMemcpyHostToDevice));
+  int rc = upload_schedule(e);
+  if (rc) return rc;
   return p2pg_reset(e);
+}
+
+}  // namespace
+
+extern "C" {
+
+int p2pg_set_sources(p2pg_engine* e, int32_t M, const int32_t* src) {
+  return set_sources(e, "set_sources", M, src, nullptr);
+}
+
+int p2pg_set_sources_at(p2pg_engine* e, int32_t M, const int32_t* src, const int32_t* start) {
+  if (e && !start) return fail(e, P2PG_ERR_ARG, "set_sources_at: need M > 0, src and start");
+  return set_sources(e, "set_sources_at", M, src, start);
+}
+
+int p2pg_originate(p2pg_engine* e, int64_t n, const int32_t* msg, const int32_t* peer, int32_t round) {
+  if (!e || n < 0 || (n > 0 && (!msg || !peer))) return fail(e, P2PG_ERR_ARG, "originate: bad arguments");
+  if (!e->have_state) return fail(e, P2PG_ERR_STATE, "originate: no sources set");
+  if (e->begun) return fail(e, P2PG_ERR_STATE, "originate: a round has begun (step_begin)");
+  if (partitioned(e)) return fail(e, P2PG_ERR_STATE, "originate: not on a vertex-partitioned rank");
+  if (!e->failed.empty()) return fail(e, P2PG_ERR_STATE, "originate: " + e->failed);
+  if (round < std::max<int32_t>(1, e->round))
+    return fail(e, P2PG_ERR_ARG, "originate: round " + std::to_string(round) + " is not ahead (the next round to run is " +
+                                     std::to_string(e->round) + ", and round 0 belongs to p2pg_set_sources_at)");
+  std::vector<int32_t> ms(msg, msg + n);
+  for (int64_t i = 0; i < n; ++i) {
+    if (msg[i] < 0 || msg[i] >= e->M) return fail(e, P2PG_ERR_ARG, "originate: message out of range");
+    if (peer[i] < 0 || peer[i] >= e->V) return fail(e, P2PG_ERR_ARG, "originate: peer out of range");
+    if (e->h_start[msg[i]] != -1)
+      return fail(e, P2PG_ERR_ARG, "originate: message " + std::to_string(msg[i]) + " is scheduled already (round " +
+                                       std::to_string(e->h_start[msg[i]]) + ")");
+  }
+  std::sort(ms.begin(), ms.end());
+  if (std::adjacent_find(ms.begin(), ms.end()) != ms.end())
+    return fail(e, P2PG_ERR_ARG, "originate: a message is listed twice");
+  if (n == 0) return P2PG_OK;
+  for (int64_t i = 0; i < n; ++i) {
+    e->h_src[msg[i]] = peer[i];
+    e->h_start[msg[i]] = round;
+  }
+  int rc = upload_schedule(e);
+  if (rc) return rc;
+  e->done = false;  // (an engine that had gone quiet runs on: a start lies ahead)
+  return P2PG_OK;
 }
 
 }  // extern "C"
@@ -962,15 +1123,18 @@ const SeedStats& seed_stats(p2pg_engine* e) {
   if (ss.ok) return ss;
   ss = SeedStats{};
   const bool gossip = e->cfg.mode == P2PG_MODE_GOSSIP;
-  std::vector<int64_t> vs(e->h_src.begin(), e->h_src.end());
-  std::vector<int64_t> vw(e->M);
+  std::vector<int64_t> vs, vw;  // round 0's origins: the messages with start 0
+  vs.reserve(e->M);
+  vw.reserve(e->M);
   for (int32_t m = 0; m < e->M; ++m) {
+    if (e->h_start[m] != 0) continue;
     const int64_t v = e->h_src[m];
     const int64_t d = e->h_rowptr[v + 1] - e->h_rowptr[v];
     ss.relays += gossip ? (uint64_t)std::min<int64_t>(d, e->cfg.fanout) : (uint64_t)d;
-    vw[m] = v * e->W + (m >> 6);
+    vs.push_back(v);
+    vw.push_back(v * e->W + (m >> 6));
   }
-  ss.nw = (uint64_t)e->M;
+  ss.nw = (uint64_t)vs.size();
   std::sort(vs.begin(), vs.end());
   vs.erase(std::unique(vs.begin(), vs.end()), vs.end());
   std::sort(vw.begin(), vw.end());
@@ -1168,8 +1332,14 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   e->begun = false;
   const bool gossip = e->cfg.mode == P2PG_MODE_GOSSIP;
   bool fused_round = false, up_round = false;
+  // A round with originations (start rounds > 0): they are injected into the frontier rows after
+  // the receive pass and before the pushes, so a gossip round takes the unfused schedule -- its
+  // receive pass, k_originate, then the separate push -- with whole frontier rows (a partial row
+  // cannot be ORed into) and its own counters read before the push (the last round's pushed masks
+  // do not bound words nobody pushed).  The rounds around it keep every form they have.
+  const p2pg_engine::SchedRound* const orig = sched_round(e, e->round);
   // the update / pull-only pass of this round (fused and update+push rounds set their own)
-  if (gossip && partial_frontier(e, e->skip_frontier)) p.store_f = 2;
+  if (gossip && !orig && partial_frontier(e, e->skip_frontier)) p.store_f = 2;
   uint64_t host_new = 0, host_relays = 0, host_av = 0, host_aw = 0, host_wedge = 0, host_degact = 0;
   if (e->round == 0) {
     if ((rc = timed(e, 0, [&] { return launch_zero_rows(s.F[0], e->W, e->d_src, e->M, e->stream); }))) return rc;
@@ -1196,7 +1366,7 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     // the push form, never the result), the same pass also pushes this round's receipts.
     const bool dense_pred = e->push_mode == 2 || (e->push_mode == 0 && still_dense(e));
     const bool part = e->d_gid != nullptr;  // (a rank gets here only if part_dense)
-    fused_round = (!part || part_dense(e)) && dense_pred && gossip_fused_supported(s);
+    fused_round = !orig && (!part || part_dense(e)) && dense_pred && gossip_fused_supported(s);
     if (fused_round) {
       // a frontier nobody observes is not stored: inside p2pg_run (not its last allowed
       // round), without hop/parent records
@@ -1209,7 +1379,7 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
            })))
         return rc;
     }
-  } else if (update_push_round(e, p)) {
+  } else if (!orig && update_push_round(e, p)) {
     // the first dense round after a sparse one: update and E pushes in one pass (timed with the
     // store pushes); the frontier rows follow the fused rounds' rule
     up_round = true;
@@ -1222,6 +1392,12 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   } else {
     if ((rc = timed(e, 4, [&] { return launch_gossip_update(g, s, p, e->stream); }))) return rc;
   }
+  if (orig)  // Node.send_to_nodes at the origins of this round (node.py:106-112)
+    if ((rc = timed(e, 0, [&] {
+           return launch_originate(g, s, p, e->d_sched_peer, e->d_sched_msg, e->d_sched_grp, orig->g_lo,
+                                   orig->g_hi - orig->g_lo, e->stream);
+         })))
+      return rc;
   if (s.hop)
     if ((rc = timed(e, 3, [&] {
            return launch_record(graph_for_arrivals(e, e->round), s, p, e->stream);
@@ -1257,7 +1433,7 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     // that choice is clear already) and to size the sparse push's (peer, word) list (else
     // bounded by the last round's pushed masks).  Not on a vertex-partitioned rank: rows other
     // ranks pushed arrive by the exchange, so this rank's own pushed masks bound nothing
-    const bool blind = e->round > 0 && e->push_mode != 2 && !e->d_gid && clearly_sparse(e) &&
+    const bool blind = e->round > 0 && e->push_mode != 2 && !e->d_gid && !orig && clearly_sparse(e) &&
                        e->prev_sw > 0;
     // (partitioned ranks: E for their local connections when part_dense, ghost rows travel)
     if (s.E[0] && (!e->d_gid || part_dense(e))) {
@@ -1350,9 +1526,10 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     fprintf(stderr, "\n");
   }
 #endif
-  const bool active = tot[ST_NEW] != 0;
+  // in flight, or a scheduled start lies at or after the next round
+  const bool active = tot[ST_NEW] != 0 || start_ahead(e, e->round + 1);
   e->frontier_kept_prev = e->frontier_kept;
-  e->frontier_kept = !(((fused_round || up_round) && !p.store_f) || p.store_f == 2) || !active;
+  e->frontier_kept = !(((fused_round || up_round) && !p.store_f) || p.store_f == 2) || tot[ST_NEW] == 0;
   if (out) {
     out->round = e->round;
     out->active = active ? 1 : 0;
@@ -1408,6 +1585,11 @@ static bool decay_batchable(const p2pg_engine* e) {
   return br > 1 && e->have_state && !e->done && !e->begun && e->round > 0 && !frontier_needed(e) &&
          e->cfg.mode == P2PG_MODE_GOSSIP && e->saw_dense && !e->last_push_e &&
          e->last_new < e->prev2_new && e->prev_sw > 0 && !e->consume_next && e->arr_round < 0 &&
+         // every start in round 0: a batch's list is sized for one wave's decay (each round's
+         // frontier smaller than the last); with start rounds a younger wave may still be growing
+         // under the older ones' decay and outgrow it mid-batch, and an origination round reads its
+         // own counters before its push
+         e->last_start == 0 &&
          !e->d_gid && !(e->cfg.flags & P2PG_FLAG_NO_AUTOSTOP) && e->push_mode != 2 &&
          e->auto_buf == nullptr && sparse_scatter_on(e) &&
          e->last_new * 16 < (uint64_t)e->V;  // the tail: small rounds, where the syncs dominate
@@ -1728,7 +1910,8 @@ int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32
   for (int64_t i = 0; i < n; ++i) {
     const int64_t v = (int64_t)(list[i] >> 32);
     const uint64_t deg = (uint64_t)(e->h_rowptr[v + 1] - e->h_rowptr[v]);
-    cancelled += gossip ? std::min<uint64_t>(deg, (uint64_t)e->cfg.fanout) : (r == 0 ? deg : (deg ? deg - 1 : 0));
+    const bool origin = e->h_start[(uint32_t)list[i]] == r;  // the message's own origination
+    cancelled += gossip ? std::min<uint64_t>(deg, (uint64_t)e->cfg.fanout) : (origin ? deg : (deg ? deg - 1 : 0));
   }
   if (lr == hipSuccess && gossip) {
     // this round's pushes left inside the round: push the remaining receipts again, as row
@@ -1868,6 +2051,9 @@ int p2pg_set_global_ids(p2pg_engine* e, const int32_t* gid) {
   if (tally_on(e))
     return fail(e, P2PG_ERR_STATE, "set_global_ids: a P2PG_FLAG_TALLY engine cannot be a vertex-partitioned "
                                    "rank (ghost rows would be counted on two ranks)");
+  if (gid && e->have_state && e->late)
+    return fail(e, P2PG_ERR_STATE, "set_global_ids: start rounds other than 0 are not available on a "
+                                   "vertex-partitioned rank");
   HIPCHK(e, hipSetDevice(e->cfg.device));
   dfree(e->d_gid);
   e->h_gid.clear();
@@ -2322,6 +2508,9 @@ int p2pg_snapshot(p2pg_engine* e, void* buf, int64_t cap) {
   if (!e->have_state) return fail(e, P2PG_ERR_STATE, "snapshot: no sources set");
   if (tally_on(e))
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold run tallies (P2PG_FLAG_TALLY)");
+  if (e->late)
+    return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold start rounds other than 0 "
+                                   "(p2pg_set_sources_at / p2pg_originate)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "snapshot: a round has begun (step_begin)");
   if (e->arr_round >= 0 && e->arr_round == e->round)
     return fail(e, P2PG_ERR_STATE, "snapshot: take it before a topology update or after the next round");
@@ -2385,6 +2574,9 @@ int p2pg_restore(p2pg_engine* e, const void* buf, int64_t size) {
   if (!e->have_state) return fail(e, P2PG_ERR_STATE, "restore: set the same sources first");
   if (tally_on(e))
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold run tallies (P2PG_FLAG_TALLY)");
+  if (e->late)
+    return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold start rounds other than 0 "
+                                   "(p2pg_set_sources_at / p2pg_originate)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "restore: a round has begun (step_begin)");
   SnapHeader h;
   std::memcpy(&h, buf, sizeof(h));

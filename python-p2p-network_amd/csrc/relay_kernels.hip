@@ -54,6 +54,7 @@ __global__ void k_zero_rows(uint64_t* plane, int32_t W, const int32_t* rows, int
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)n * W) return;
   const int64_t r = rows[i / W];
+  if (r < 0) return;  // (a message that does not originate in round 0)
   plane[r * W + (i % W)] = 0ull;
 }
 
@@ -61,6 +62,7 @@ __global__ void k_seed(DevState st, const int32_t* src, int32_t M) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= M) return;
   const int64_t v = src[m];
+  if (v < 0) return;  // (a message that does not originate in round 0)
   const uint64_t bit = 1ull << (m & 63);
   const int64_t o = v * st.W + (m >> 6);
   atomicOr((unsigned long long*)&st.F[0][o], (unsigned long long)bit);
@@ -2130,7 +2132,7 @@ __global__ __launch_bounds__(256, P2PG_FUSED_WAVES) void k_gossip_fused(DevGraph
 // ---------------------------------------------------------------------------------------
 // Validation: the lowest-id neighbour v whose round-(r-1) send of message m reached u
 // (receivers process senders in ascending id -- the harness's stand-in for TCP arrival
-// order).  Returns -2 if none (cannot happen for a first receipt at r >= 1).
+// order).  Returns -2 if none: the receipt is the message's own origination (its start round).
 __device__ int32_t find_parent(const DevGraph& g, const DevState& st, const RoundParams& p,
                                int64_t u, int m) {
   const int prv = (p.round & 1) ^ 1;
@@ -2196,7 +2198,8 @@ __global__ __launch_bounds__(256) void k_record(DevGraph g, DevState st, RoundPa
           f &= f - 1ull;
           const int m = w * 64 + bit;
           st.hop[u * st.M + m] = p.round;
-          st.parent[u * st.M + m] = p.round == 0 ? -1 : find_parent(g, st, p, u, m);
+          const int32_t par = p.round == 0 ? -1 : find_parent(g, st, p, u, m);
+          st.parent[u * st.M + m] = par < 0 ? -1 : par;  // (no sender: an origination)
         }
       }
     }
@@ -2231,7 +2234,8 @@ __global__ __launch_bounds__(256) void k_deliveries(DevGraph g, DevState st, Rou
           if ((int64_t)pos < cap) {
             peer[pos] = (int32_t)u;
             msg[pos] = m;
-            parent[pos] = p.round == 0 ? -1 : find_parent(g, st, p, u, m);
+            const int32_t par = p.round == 0 ? -1 : find_parent(g, st, p, u, m);
+            parent[pos] = par < 0 ? -1 : par;  // (no sender: an origination)
           }
         }
       }

@@ -160,6 +160,10 @@ class GraphNetwork:
         self._h = h
         self._check(L.p2pg_load_csr(h, graph.V, _lib.ptr(graph.rowptr), _lib.ptr(graph.colidx)))
         self.sources = None
+        self.start_rounds = None     # int32 [M]: the round each broadcast originates in (-1 = unscheduled)
+        self._autostop = bool(autostop)
+        self._next_round = 0         # the next round the engine runs
+        self._quiet = False          # the engine went quiet (further steps run no round)
         self.rounds = []
         self.message_count_send = 0  # sum of Node.message_count_send (node.py:65, :116)
         self._run_buf = None
@@ -198,21 +202,63 @@ class GraphNetwork:
         self._check(_lib.lib().p2pg_set_stream(self._h, ctypes.c_void_p(hip_stream or None)))
 
     # -- broadcasts -----------------------------------------------------------------------
-    def broadcast(self, sources):
+    def broadcast(self, sources, start_rounds=None):
         """Originate one broadcast per entry (origin peer ids); message m = position m.
-        Equivalent of calling Node.send_to_nodes(data) at each origin (node.py:106)."""
-        src = np.ascontiguousarray(sources, dtype=np.int32)
+        Equivalent of calling Node.send_to_nodes(data) at each origin (node.py:106).
+
+        ``start_rounds[m]`` is the round message m originates in (default: all in round 0): in
+        that round, after its arrivals, the origin makes a first receipt (hop = the round,
+        parent -1) and sends to all its connections (flood) or its ``fanout`` picks (gossip).
+        -1 in both arrays declares an unscheduled message, to be started by ``originate``.
+        ``run`` crosses the idle rounds before a scheduled start; hops stay absolute round
+        indices (``hop_parent(relative=True)`` subtracts the start rounds)."""
+        src = np.array(sources, dtype=np.int32, ndmin=1)
         if src.ndim != 1 or len(src) == 0:
             raise ValueError("sources must be a non-empty 1-D array of peer ids")
-        self._check(_lib.lib().p2pg_set_sources(self._h, len(src), _lib.ptr(src)))
+        if start_rounds is None:
+            self._check(_lib.lib().p2pg_set_sources(self._h, len(src), _lib.ptr(src)))
+            start = np.zeros(len(src), dtype=np.int32)
+        else:
+            start = np.array(start_rounds, dtype=np.int32, ndmin=1)
+            if start.shape != src.shape:
+                raise ValueError("start_rounds must have one entry per source")
+            self._check(_lib.lib().p2pg_set_sources_at(self._h, len(src), _lib.ptr(src), _lib.ptr(start)))
         self.sources = src
+        self.start_rounds = start
         self.rounds = []
         self.message_count_send = 0
+        self._next_round, self._quiet = 0, False
+
+    def originate(self, msgs, peers, round=None):
+        """Between rounds: start the unscheduled broadcasts ``msgs`` at ``peers`` in ``round``
+        (default: the next round to run) -- the send_to_nodes(data) an app decides on while it
+        runs, e.g. a reply made in ``node_message_batch`` (p2pg_originate).  Wakes a network
+        that had gone quiet: ``run`` / ``step`` continue."""
+        m = np.array(msgs, dtype=np.int32, ndmin=1)
+        p = np.array(peers, dtype=np.int32, ndmin=1)
+        if m.ndim != 1 or m.shape != p.shape:
+            raise ValueError("msgs and peers must be 1-D arrays of the same length")
+        if round is None:
+            round = max(1, self._next_round)
+        self._check(_lib.lib().p2pg_originate(self._h, len(m), _lib.ptr(m) if len(m) else None,
+                                              _lib.ptr(p) if len(p) else None, int(round)))
+        self.sources[m] = p
+        self.start_rounds[m] = int(round)
+        if len(m):
+            self._quiet = False
 
     def reset(self):
+        """Back to round 0 with the same sources and start rounds (``originate`` included)."""
         self._check(_lib.lib().p2pg_reset(self._h))
         self.rounds = []
         self.message_count_send = 0
+        self._next_round, self._quiet = 0, False
+
+    def _ran(self, st):
+        """Book-keeping of the next round to run (``originate``'s default) after round stats st."""
+        if not self._quiet:
+            self._next_round = st.round + 1
+            self._quiet = self._autostop and not st.active
 
     def step_begin(self):
         """Start the next round asynchronously: on a vertex-partitioned rank, the peers with no
@@ -229,6 +275,7 @@ class GraphNetwork:
         st = RoundStats.from_c(s)
         self.rounds.append(st)
         self.message_count_send += st.relays
+        self._ran(st)
         if st.new_deliveries and self._wants_deliveries():
             self.node_message_batch(self.deliveries())
         return st
@@ -248,6 +295,8 @@ class GraphNetwork:
                 out.extend(got)                              # if the call failed
                 self.rounds.extend(got)
                 self.message_count_send += sum(st.relays for st in got)
+                if got:
+                    self._ran(got[-1])
                 rc = self._check(rc)
                 if rc == 0 or n.value == 0:
                     break
@@ -293,8 +342,10 @@ class GraphNetwork:
         b = np.ascontiguousarray(buf, dtype=np.uint8)
         self._check(_lib.lib().p2pg_restore(self._h, _lib.ptr(b), len(b)))
         self.rounds = []
-        self.message_count_send = int(np.frombuffer(b[:128].tobytes(), dtype=np.uint64)[
-            _SNAP_TOTAL_RELAYS_WORD])
+        head = np.frombuffer(b[:128].tobytes(), dtype=np.uint64)
+        self.message_count_send = int(head[_SNAP_TOTAL_RELAYS_WORD])
+        self._next_round = int(head[5] >> np.uint64(32))        # SnapHeader.round
+        self._quiet = self._autostop and bool(head[7] >> np.uint64(32))  # SnapHeader.done
 
     def save_snapshot(self, path):
         np.save(path, self.snapshot(), allow_pickle=False)
@@ -362,9 +413,10 @@ class GraphNetwork:
             raise ValueError("peer and msg must have the same length")
         self._check(_lib.lib().p2pg_drop_relays(self._h, len(p), _lib.ptr(p) if len(p) else None,
                                                 _lib.ptr(m) if len(m) else None))
-        drop = sum(min(self.fanout, d) if self.mode == "gossip" else
-                   (d if self.rounds and self.rounds[-1].round == 0 else max(d - 1, 0))
-                   for d in self.graph.degree()[p].tolist())
+        last = self.rounds[-1].round if self.rounds else -1
+        origin = (self.start_rounds[m] == last).tolist()  # a message's own origination: all deg
+        drop = sum(min(self.fanout, d) if self.mode == "gossip" else (d if o else max(d - 1, 0))
+                   for d, o in zip(self.graph.degree()[p].tolist(), origin))
         self.message_count_send -= drop
 
     # -- validation planes ----------------------------------------------------------------
@@ -396,7 +448,9 @@ class GraphNetwork:
 
     def message_tally(self):
         """MessageTally(reach, hop_sum, last_hop) per broadcast, accumulated from every round's
-        first receipts; needs tally=True (p2pg_message_tally)."""
+        first receipts; needs tally=True (p2pg_message_tally).  Hops are absolute round indices:
+        for a broadcast that started late, the mean hop counted from its own start is
+        ``hop_sum / reach - start_rounds`` and its last hop ``last_hop - start_rounds``."""
         reach = np.zeros(self.M, dtype=np.uint64)
         hop_sum = np.zeros(self.M, dtype=np.uint64)
         last_hop = np.zeros(self.M, dtype=np.int32)
@@ -414,13 +468,17 @@ class GraphNetwork:
         self._check(_lib.lib().p2pg_peer_counters(self._h, _lib.ptr(sent), _lib.ptr(received)))
         return PeerCounters(sent, received)
 
-    def hop_parent(self):
-        """(hop, parent) int32 [V, M]; needs record=True.  -1 = not delivered / origin."""
+    def hop_parent(self, relative=False):
+        """(hop, parent) int32 [V, M]; needs record=True.  -1 = not delivered / origin.  Hops are
+        absolute round indices; ``relative=True`` subtracts each broadcast's start round from its
+        delivered hops (-1 stays -1)."""
         if not self.record:
             raise RuntimeError("hop/parent planes need GraphNetwork(record=True)")
         hop = np.zeros((self.graph.V, self.M), dtype=np.int32)
         par = np.zeros_like(hop)
         self._check(_lib.lib().p2pg_read_planes(self._h, None, _lib.ptr(hop), _lib.ptr(par)))
+        if relative:
+            hop = np.where(hop >= 0, hop - self.start_rounds[None, :], -1).astype(np.int32)
         return hop, par
 
     KERNEL_CLASSES = ("seed", "flood_pull", "gossip_scatter_atomic", "record", "gossip_update",
