@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "device_util.h"
+#include "pass_plan.h"
 
 // Dense pushes: the folded-round Philox of one source's draws (philox_pick); 0 = the generic
 // philox4x32_10 per draw (A/B builds)
@@ -1530,6 +1531,127 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
   PROF_MARK(8);
 }
 
+// The push of a wide sender (GCHUNK < deg <= HUB_T) of a fused round by the pass plan of
+// pass_plan.h (no churn, compile-time fanout, packed E rows): the entry list is built once per
+// list window, and every (peer, message) pick is evaluated once per group of 64 connections
+// instead of once per GCHUNK-connection chunk.  Per group the active words are cut by rank into
+// passes that fit the LDS table; a pass runs the picks of its words' contiguous sub-list (the
+// list is word-major) and flushes those words of every connection of the group.
+// Table of a pass: 64-bit masks [connection][rank in pass], row stride seg = the flush segment,
+// so the flush reads it linearly (mask t*64 + lane in trip t: one 64-bit LDS read, no bank
+// conflicts) and one store covers 64 / seg connections; the picks of a batch OR into random
+// connections' rows either way.  rv0 = the receiver slots of the first 64 connections.
+#ifndef P2PG_WIDE_PASS
+#define P2PG_WIDE_PASS 1
+#endif
+template <int K, class CT>
+__device__ __forceinline__ void scatter_wide(const DevGraph& g, const DevState& st,
+                                             const RoundParams& p, ScatterLds& L, int lane,
+                                             int64_t v, uint32_t beg, uint32_t deg, uint64_t f,
+                                             uint32_t rv0, CT* c PROF_PARAMS) {
+  static_assert(K > 0, "compile-time fanout only");
+  static_assert(GCHUNK * 128 >= PLAN_CELLS, "the pass plan's table");
+  const int W = st.W;
+  uint64_t* __restrict__ Eo = st.E[p.round & 1];
+  const uint64_t fam = __ballot(f != 0ull);  // active words (the caller saw one)
+  const int nf = __popcll(fam);
+  const uint32_t gv = gidx_s(g, v);
+  const PickKey pkey = pick_key((uint32_t)p.round, gv, p.gseed_lo, p.gseed_hi);
+  // word-major entry list: lane w's bits at its exclusive prefix of popcounts
+  const uint32_t cnt = (uint32_t)__popcll(f);
+  const uint32_t incl = wave_scan_u32(cnt);
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  const uint32_t pos0 = incl - cnt;
+  // lane r: the list position of the first entry of the word of rank r (r < nf; the inactive
+  // words write lane 63, which is rank 63 only when every word is active)
+  const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(fam >> 32),
+                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)fam, 0u));
+  const uint32_t rpos = (uint32_t)__builtin_amdgcn_ds_permute((f ? rank : 63) << 2, (int)pos0);
+  constexpr uint32_t CAP = (uint32_t)GLIST - 1u;  // entries per list window (see scatter_row)
+  uint32_t have = ~0u;                            // first entry of the window in L.lst
+  // several groups: picks outside the group are dropped (one group: the bound Cc below is no
+  // bound -- one compare either way, and no flag live across the Philox rounds)
+  const bool check = deg > (uint32_t)PLAN_GROUP;
+
+  for (uint32_t cb = 0; cb < deg; cb += PLAN_GROUP) {
+    const int C = (int)(deg - cb < (uint32_t)PLAN_GROUP ? deg - cb : (uint32_t)PLAN_GROUP);
+    uint32_t rv = rv0;
+    if (cb) {  // the group's receiver slots, waited for right here (see k_gossip_fused)
+      const uint32_t j = beg + cb + (uint32_t)lane;
+      rv = j < beg + deg ? g.rev[j] : 0u;
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    }
+    const int wp = plan_pass_words(C);
+    const uint32_t Cc = check ? (uint32_t)C : ~0u;
+    for (int r0 = 0; r0 < nf; r0 += wp) {
+      const int nr = nf - r0 < wp ? nf - r0 : wp;
+      const int seg = plan_seg(nr);
+      const int nmask = C * seg;  // <= PLAN_MASKS
+      uint64_t* const tb = reinterpret_cast<uint64_t*>(L.tbl);
+      for (int i = lane; i < nmask; i += 64) tb[i] = 0ull;
+      // the pass's entries: list positions [s, e)
+      const uint32_t s = (uint32_t)__builtin_amdgcn_readlane((int)rpos, r0);
+      const uint32_t e = r0 + nr < nf ? (uint32_t)__builtin_amdgcn_readlane((int)rpos, r0 + nr) : total;
+      for (uint32_t lb = 0; lb < e; lb += CAP) {
+        if (lb + CAP <= s) continue;
+        if (lb != have) {
+          wave_lds_sync();  // (readers of the window before)
+          list_bits(L.lst, CAP, f, (uint32_t)lane << 6, pos0 - lb, total - lb < CAP ? total - lb : CAP);
+          have = lb;
+        }
+        wave_lds_sync();  // the list and the table clear, before the picks
+        PROF_MARK(6);
+        const uint32_t a = (s > lb ? s : lb) - lb;
+        const uint32_t n = (e < lb + CAP ? e : lb + CAP) - lb - a;
+        // strided batches with a uniform trip count, as scatter_row's pick_batch
+        const uint32_t nbat = (n + 63) >> 6;
+        const uint32_t i0 = (uint32_t)lane * nbat;
+        const uint32_t mine = i0 < n ? (n - i0 < nbat ? n - i0 : nbat) : 0u;
+        auto at = [&](uint32_t i) { return a + i < (uint32_t)GLIST ? a + i : (uint32_t)GLIST - 1u; };
+        uint32_t en = L.lst[at(i0)];
+        for (uint32_t b = 0; b < nbat; ++b) {
+          const uint32_t ent = en & 0x0FFFu;  // in range even when stale
+          en = L.lst[at(i0 + b + 1)];
+          const uint32_t wl = ent >> 6, bit = ent & 63u;
+          const uint32_t mg = p.msg_base + wl * 64u + bit;
+          // the word's rank in the pass (a stale entry's may be any: masked into the segment)
+          const uint32_t rr = ((uint32_t)__popcll(fam & ((1ull << wl) - 1ull)) - (uint32_t)r0) &
+                              (uint32_t)(seg - 1);
+          uint32_t* const col = &L.tbl[rr * 2u + (bit >> 5)];
+          const uint32_t mb = b < mine ? 1u << (bit & 31u) : 0u;
+          uint32_t pk[K];
+          if constexpr (P2PG_PICK_FOLD && K <= 4)
+            gossip_picks_k<K>(pkey, mg, deg, pk);
+          else
+            gossip_picks_t<K>((uint32_t)p.round, gv, mg, deg, p.gseed_lo, p.gseed_hi, pk);
+#pragma unroll
+          for (int q = 0; q < K; ++q) {
+            const uint32_t jj = pk[q] - cb;
+            if (jj < Cc) atomicOr(col + jj * (uint32_t)(seg * 2), mb);
+          }
+        }
+        wave_lds_sync();
+        PROF_MARK(7);
+      }
+      // flush: mask t*64 + lane = (connection, rank) = (that / seg, that % seg)
+      const int rk_lane = lane & (seg - 1);
+      const int gl = lane / seg;  // (seg: 16, 32 or 64)
+      const int gper = 64 / seg;
+      for (int j0 = 0; j0 < C; j0 += gper) {
+        const int jj = j0 + gl;
+        const bool ok = rk_lane < nr && jj < C;
+        const uint64_t x = ok ? tb[j0 * seg + lane] : 0ull;
+        const uint32_t nj = (uint32_t)__builtin_amdgcn_ds_bpermute((jj < C ? jj : 0) << 2, (int)rv);
+        const uint64_t bal = __ballot(x != 0ull);
+        if (ok) st_row(at_row(Eo, nj, W) + r0 + rk_lane, x);
+        if (lane == 0) c[ST_SCATTER] += (CT)__popcll(bal);
+      }
+      wave_lds_sync();  // (the next pass clears the table)
+      PROF_MARK(8);
+    }
+  }
+}
+
 // The scatter launch: tasks [task0, nwords) are 32-peer bitmap words (sources with deg <=
 // GCHUNK), tasks from nwords on are groups of 64 (wide source, chunk) items.  task0 = nwords
 // runs the items only (fused rounds: the items of the pull hubs, deg > HUB_T).
@@ -2080,7 +2202,7 @@ __global__ __launch_bounds__(256, P2PG_FUSED_WAVES) void k_gossip_fused(DevGraph
       // target's gathers included.
       if (PL) {
         // (no pushes: the sparse push that follows reads the frontier row)
-      } else if (deg <= (uint64_t)GCHUNK) {
+      } else if (__builtin_expect(deg <= (uint64_t)GCHUNK, 1)) {  // (94 % of the peers)
         scatter_row<CHURN, K, true, 1, PART, PO || UP>(g, st, p, lds[wib], lane, u, a.beg, (int64_t)deg, 0, 0,
                                        nw, a.rv, 0, c PROF_PASS);
         pend = true;
@@ -2089,6 +2211,10 @@ __global__ __launch_bounds__(256, P2PG_FUSED_WAVES) void k_gossip_fused(DevGraph
         pdeg = (int64_t)deg;
         pnw = nw;
         prcv = a.rv;
+      } else if constexpr (P2PG_WIDE_PASS && !CHURN && K > 0 && !PART) {
+        // by the pass plan: every pick evaluated once per 64 connections (churn draws are per
+        // connection and generic fanout / partitioned ranks are rare: those stay chunked)
+        scatter_wide<K>(g, st, p, lds[wib], lane, u, a.beg, (uint32_t)deg, nw, a.rv, c PROF_PASS);
       } else if (deg <= 64) {
         for (int ch = 0; (int64_t)ch * GCHUNK < (int64_t)deg; ++ch)
           scatter_row<CHURN, K, true, 0, PART, PO || UP>(g, st, p, lds[wib], lane, u, a.beg, (int64_t)deg, ch, 0,
