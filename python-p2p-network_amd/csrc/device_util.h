@@ -16,10 +16,7 @@ namespace {
 
 constexpr int WPB = 4;  // waves per block (256 threads)
 // Sparse-round kernels scan this many task words per wave pass, one per lane
-#ifndef P2PG_SCAN_W
-#define P2PG_SCAN_W 4
-#endif
-constexpr int SCAN_W = P2PG_SCAN_W;
+constexpr int SCAN_W = 4;
 constexpr int GRID_MAX = 2048;
 
 __device__ __forceinline__ bool bit_test(const uint32_t* bm, int64_t v) {
@@ -81,59 +78,17 @@ __device__ __forceinline__ T ldc(const T* p) {
   return *(const __attribute__((address_space(4))) T*)p;
 }
 
-// Per-connection E stores of the gossip dense rounds are non-temporal: the planes are re-read
-// a round later, far beyond L2 / MALL reach, and nt stores retire sooner -- which matters
-// because a wave's next gather wait (vmcnt, in order) also waits for its in-flight stores
-// (c4 A/B: fused rounds 267.9 -> 258.7 ms per step).  P2PG_NT_STORE=0 restores plain stores.
-// P2PG_NT_ROWS / P2PG_NT_LOADS extend nt to the fused kernel's seen / frontier row stores and
-// to its E gathers (read once per receiver): together another 260.6 -> 258.7 ms (3 interleaved
-// pairs).
-#ifndef P2PG_NT_STORE
-#define P2PG_NT_STORE 1
-#endif
-#ifndef P2PG_NT_ROWS
-#define P2PG_NT_ROWS 1
-#endif
-#ifndef P2PG_NT_LOADS
-#define P2PG_NT_LOADS 1
-#endif
-#ifndef P2PG_NT_ISSUE
-#define P2PG_NT_ISSUE 0
-#endif
-// streamed-once loads of the fused kernel's row stage (seen word, neighbour ids, receiver slots);
-// nt here measured ±0 (3 interleaved c4 pairs), so off by default
-template <class T>
-__device__ __forceinline__ T ld_once(const T* p) {
-#if P2PG_NT_ISSUE
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
+// The round kernels (pull, update, scatter, fused, grouped) store their rows non-temporally in
+// every plane they write: the per-connection E rows of the gossip dense rounds, the seen and
+// frontier rows, and the cleared push rows.  These planes are re-read a round later, far beyond L2 / MALL reach, and nt stores
+// retire sooner -- which matters because a wave's next gather wait (vmcnt, in order) also waits
+// for its in-flight stores (c4 A/B: E stores, fused rounds 267.9 -> 258.7 ms per step; the fused
+// kernel's seen / frontier rows and nt E gathers, read once per receiver, 260.6 -> 258.7 ms; the
+// pull and update kernels' rows, c4 update kernel 13.3 -> 12.7 ms, c3 flood pull unchanged).
+// The loads of the fused kernel's row stage (seen word, neighbour ids, receiver slots) stay
+// plain: nt there measured +-0 (3 interleaved c4 pairs).
 __device__ __forceinline__ void st_row(uint64_t* p, uint64_t x) {
-#if P2PG_NT_STORE
   __builtin_nontemporal_store(x, p);
-#else
-  *p = x;
-#endif
-}
-#ifndef P2PG_NT_PULL
-#define P2PG_NT_PULL 1  // c4 update kernel 13.3 -> 12.7 ms per step; c3 flood pull unchanged
-#endif
-// seen / frontier / push-row stores of the pull and update kernels, non-temporal too
-__device__ __forceinline__ void st_prow(uint64_t* p, uint64_t x) {
-#if P2PG_NT_PULL
-  __builtin_nontemporal_store(x, p);
-#else
-  *p = x;
-#endif
-}
-__device__ __forceinline__ void st_frow(uint64_t* p, uint64_t x) {
-#if P2PG_NT_ROWS
-  __builtin_nontemporal_store(x, p);
-#else
-  *p = x;
-#endif
 }
 
 // Row r of a [rows][W] plane for a per-lane row id.  Row ids (peers, and E slots: rev[] holds
@@ -306,30 +261,62 @@ int grid_tasks(int64_t ntasks) {
 }
 
 // Grid for the per-peer pull kernels, whose task cost is very uneven (power-law degrees,
-// receipts per peer): P2PG_FUSED_GRID (default 32) x the blocks resident at once, so that
+// receipts per peer): FUSED_GRID_MUL x the blocks resident at once, so that
 // blocks finishing early are replaced (measured on config 4: 2x -> 300 ms, 8x -> 267 ms,
 // 32x -> 260 ms for the fused rounds).
+constexpr int FUSED_GRID_MUL = 32;
 // The fused / grouped kernels keep their per-wave round totals in 32 bits.  A 32-peer task adds
 // at most 32 peers x 4096 messages x fanout 16 = 2^21 to any of them (relays; hubs, deg > HUB_T,
 // never go through these kernels, so wedges <= 32 x 64 words x 512 = 2^20), so a wave may take
 // at most 2^10 tasks (2^10 x 2^21 = 2^31 < 2^32, strictly): the grid is never smaller than that
-// bound asks, whatever P2PG_FUSED_GRID, the device size or V (config 4: ~2.4 tasks per wave).
+// bound asks, whatever the device size or V (config 4: ~2.4 tasks per wave).
 constexpr int64_t TASKS_PER_WAVE_MAX = 1024;
 static_assert(TASKS_PER_WAVE_MAX * (int64_t{32} * 4096 * 16) < (int64_t{1} << 32),
               "per-wave 32-bit round totals could wrap");
 
 template <class F>
 int balanced_grid(F kernel, int64_t ntasks) {
-  static const int gmul = [] {
-    const char* e = std::getenv("P2PG_FUSED_GRID");
-    const int v = e ? std::atoi(e) : 32;
-    return v > 0 ? v : 32;
-  }();
   const int64_t full = (int64_t)grid_tasks_uncapped(ntasks);
   const int64_t floor32 = (ntasks + TASKS_PER_WAVE_MAX * WPB - 1) / (TASKS_PER_WAVE_MAX * WPB);
-  return (int)std::min<int64_t>(full, std::max<int64_t>((int64_t)gmul * resident_blocks(kernel), floor32));
+  return (int)std::min<int64_t>(full, std::max<int64_t>((int64_t)FUSED_GRID_MUL * resident_blocks(kernel), floor32));
 }
 
+// The launchers' template dispatch: f(CH, K) with CH = std::bool_constant<churn on> and K =
+// std::integral_constant<int, fanout> for the compile-time fanouts 1..4, <int, 0> for any other
+// (the kernels then read p.fanout).
+template <class F>
+void dispatch_fanout_churn(const RoundParams& p, F&& f) {
+  auto churn = [&](auto k) {
+    if (p.churn_thr != 0) f(std::true_type{}, k); else f(std::false_type{}, k);
+  };
+  switch (p.fanout) {
+    case 1: churn(std::integral_constant<int, 1>{}); break;
+    case 2: churn(std::integral_constant<int, 2>{}); break;
+    case 3: churn(std::integral_constant<int, 3>{}); break;
+    case 4: churn(std::integral_constant<int, 4>{}); break;
+    default: churn(std::integral_constant<int, 0>{}); break;
+  }
+}
+
+// ceil(log2(W)): a row of W words takes 1 << log2_ceil(W) lanes per peer.
+inline int log2_ceil(int W) {
+  int lw = 0;
+  while ((1 << lw) < W) ++lw;
+  return lw;
+}
+
+// f(std::integral_constant<int, LW>) for the log-width lw of a row of at most 32 words (0..5).
+template <class F>
+void dispatch_log_width(int lw, F&& f) {
+  switch (lw) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 5>{}); break;
+  }
+}
 
 }  // namespace
 }  // namespace p2pg

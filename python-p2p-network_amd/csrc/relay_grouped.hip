@@ -32,10 +32,8 @@ namespace {
 
 constexpr int GLIST_G = 1024;  // new bits listed per pick pass (a peak-round batch: ~700)
 // E-row gathers per lane issued one batch ahead (and per round trip after that)
-#ifndef P2PG_GFG
-#define P2PG_GFG 6  // c4 A/B (profiles/r03/ab_gfg.txt): W = 8 fused 49.7 -> 47.7 ms, W = 16 97.2 -> 94.1 ms; 8 spills
-#endif
-constexpr int GFG = P2PG_GFG;
+// c4 A/B (profiles/r03/ab_gfg.txt): W = 8 fused 49.7 -> 47.7 ms, W = 16 97.2 -> 94.1 ms; 8 spills
+constexpr int GFG = 6;
 
 template <int LW>
 struct GroupedLds {
@@ -69,9 +67,7 @@ struct GStage {
   bool rcv;           // slot exists and its owner peer is processed
 };
 
-#ifndef P2PG_GROUPED_WAVES
-#define P2PG_GROUPED_WAVES 4  // <= 128 VGPRs
-#endif
+constexpr int GROUPED_WAVES = 4;  // waves per SIMD the launch bounds ask for: <= 128 VGPRs
 // PO (push only): the first dense round after an update -- the batch peers are the round's
 // active peers, their arrivals are their own frontier rows F[r&1] (dedup, counters, bitmaps were
 // done by the update), and only the picks and the flush run (replaces one wave per source with
@@ -81,7 +77,7 @@ struct GStage {
 // row atomics afterwards).  The one-peer-per-wave pull (k_pull1) spends a whole wave visit on
 // every peer with 8 of 64 lanes busy at W = 8.
 template <bool CHURN, int K, int LW, bool PO = false, bool PL = false>
-__global__ __launch_bounds__(256, P2PG_GROUPED_WAVES) void k_gossip_fused_grouped(DevGraph g, DevState st, RoundParams p) {
+__global__ __launch_bounds__(256, GROUPED_WAVES) void k_gossip_fused_grouped(DevGraph g, DevState st, RoundParams p) {
   using Lds = GroupedLds<LW>;
   // never partitioned and never on a pre-update graph (the engine's dense rounds): the id
   // translation and lost-slot tests fold away
@@ -163,7 +159,7 @@ __global__ __launch_bounds__(256, P2PG_GROUPED_WAVES) void k_gossip_fused_groupe
       q.rb1 = (uint32_t)__builtin_amdgcn_readlane((int)rp, b0 + n);
       const bool mine = gl < n && ((todo >> (b0 + gl)) & 1u);
       // PO: the peer's frontier row (its new receipts) instead of its seen row
-      if (mine && wvalid) q.s = ld_once(&(PO ? Fc : st.seen)[(u0 + b0 + gl) * W + wl]);
+      if (mine && wvalid) q.s = (PO ? Fc : st.seen)[(u0 + b0 + gl) * W + wl];
       // batch peer owning slot rb0 + lane: the number of later row starts at or below it
       // (32-bit offsets relative to the batch; a batch spans <= TS slots or one peer)
       const uint32_t rel = (uint32_t)(rp - rb0);
@@ -172,8 +168,8 @@ __global__ __launch_bounds__(256, P2PG_GROUPED_WAVES) void k_gossip_fused_groupe
         gj += (uint32_t)__builtin_amdgcn_readlane((int)rel, b0 + i) <= (uint32_t)lane;
       q.rcv = rb0 + (uint32_t)lane < q.rb1 && ((todo >> (b0 + gj)) & 1u);
       if (q.rcv) {
-        q.v = ld_once(&g.colidx[rb0 + (uint32_t)lane]);
-        q.rv = ld_once(&g.rev[rb0 + (uint32_t)lane]);
+        q.v = g.colidx[rb0 + (uint32_t)lane];
+        q.rv = g.rev[rb0 + (uint32_t)lane];
       }
     };
     auto activity = [&](GStage& q) {
@@ -348,8 +344,8 @@ __global__ __launch_bounds__(256, P2PG_GROUPED_WAVES) void k_gossip_fused_groupe
       const uint64_t wm_all = __ballot(nw != 0ull);
       const uint32_t grp = (uint32_t)((wm_all >> (gl * WP)) & gmask);  // my peer's active words
       if (!PO) {
-        if (nw) st_frow(&st.seen[u * W + wl], a.s | nw);
-        if (mine && grp && wvalid && p.store_f) st_frow(&Fc[u * W + wl], nw);
+        if (nw) st_row(&st.seen[u * W + wl], a.s | nw);
+        if (mine && grp && wvalid && p.store_f) st_row(&Fc[u * W + wl], nw);
         if (nw) {
           const uint32_t pc = (uint32_t)__popcll(nw);
           c[ST_NEW] += pc;
@@ -484,20 +480,10 @@ __global__ __launch_bounds__(256, P2PG_GROUPED_WAVES) void k_gossip_fused_groupe
 
 template <bool CH, int KT, bool PO = false, bool PL = false>
 hipError_t launch_lw(int lw, const DevGraph& g, const DevState& st, const RoundParams& p, hipStream_t s) {
-  const int64_t ntasks = (g.V + 31) >> 5;
-#define P2PG_GROUPED(LWV)                                                                    \
-  hipLaunchKernelGGL((k_gossip_fused_grouped<CH, KT, LWV, PO, PL>),                        \
-                     dim3(balanced_grid(k_gossip_fused_grouped<CH, KT, LWV, PO, PL>, ntasks)), dim3(256), \
-                     0, s, g, st, p)
-  switch (lw) {
-    case 0: P2PG_GROUPED(0); break;
-    case 1: P2PG_GROUPED(1); break;
-    case 2: P2PG_GROUPED(2); break;
-    case 3: P2PG_GROUPED(3); break;
-    case 4: P2PG_GROUPED(4); break;
-    default: P2PG_GROUPED(5); break;
-  }
-#undef P2PG_GROUPED
+  dispatch_log_width(lw, [&](auto lwc) {
+    const auto kernel = k_gossip_fused_grouped<CH, KT, decltype(lwc)::value, PO, PL>;
+    hipLaunchKernelGGL(kernel, dim3(balanced_grid(kernel, (g.V + 31) >> 5)), dim3(256), 0, s, g, st, p);
+  });
   return hipGetLastError();
 }
 
@@ -511,8 +497,7 @@ static bool packed_ok(const DevState& st, int lw, int prv) {
 hipError_t launch_gossip_fused_grouped(const DevGraph& g, const DevState& st, const RoundParams& p,
                                        hipStream_t s) {
   if (st.W > 32 || st.W < 1) return hipErrorInvalidValue;
-  int lw = 0;
-  while ((1 << lw) < st.W) ++lw;
+  const int lw = log2_ceil(st.W);
   if (!packed_ok(st, lw, (p.round & 1) ^ 1)) return hipErrorInvalidValue;
   const bool ch = p.churn_thr != 0;
   if (p.fanout == 3) return ch ? launch_lw<true, 3>(lw, g, st, p, s) : launch_lw<false, 3>(lw, g, st, p, s);
@@ -522,8 +507,7 @@ hipError_t launch_gossip_fused_grouped(const DevGraph& g, const DevState& st, co
 hipError_t launch_gossip_push_grouped(const DevGraph& g, const DevState& st, const RoundParams& p,
                                       hipStream_t s) {
   if (st.W > GROUPED_W_MAX || st.W < 1) return hipErrorInvalidValue;
-  int lw = 0;
-  while ((1 << lw) < st.W) ++lw;
+  const int lw = log2_ceil(st.W);
   if (!packed_ok(st, lw, p.round & 1)) return hipErrorInvalidValue;  // (PO: the round's own rows)
   const bool ch = p.churn_thr != 0;
   if (p.fanout == 3)
@@ -534,8 +518,7 @@ hipError_t launch_gossip_push_grouped(const DevGraph& g, const DevState& st, con
 hipError_t launch_gossip_pull_grouped(const DevGraph& g, const DevState& st, const RoundParams& p,
                                       hipStream_t s) {
   if (st.W > GROUPED_PULL_W_MAX || st.W < 1) return hipErrorInvalidValue;
-  int lw = 0;
-  while ((1 << lw) < st.W) ++lw;
+  const int lw = log2_ceil(st.W);
   if (!packed_ok(st, lw, (p.round & 1) ^ 1)) return hipErrorInvalidValue;
   // (no picks: the fanout template argument is irrelevant)
   return p.churn_thr != 0 ? launch_lw<true, 0, false, true>(lw, g, st, p, s)

@@ -30,21 +30,6 @@
 #include "device_util.h"
 #include "pass_plan.h"
 
-// Dense pushes: the folded-round Philox of one source's draws (philox_pick); 0 = the generic
-// philox4x32_10 per draw (A/B builds)
-// scatter_row<.., DIRECT>: a slice with at most one new bit per word takes its picks lane = word,
-// without the compacted list (P2PG_PICK_DIRECT=0: always the list; A/B).  Taken by the fused
-// kernel's first-dense-round modes (push-only, update + push): c4 round 10 7.4 -> 6.9 ms; in the
-// fused rounds proper the extra path cost more in the peak rounds than it saved in the light
-// ones (211.2 -> 211.9 ms per step, profiles/r06/ab_pick_direct.txt)
-#ifndef P2PG_PICK_DIRECT
-#define P2PG_PICK_DIRECT 1
-#endif
-#ifndef P2PG_PICK_FOLD
-#define P2PG_PICK_FOLD 1
-#endif
-
-
 namespace p2pg {
 namespace {
 
@@ -162,10 +147,10 @@ __global__ __launch_bounds__(256) void k_pull(DevGraph g, DevState st, RoundPara
         const bool any = __ballot(nw != 0ull) != 0ull;
         row_new |= any;
         if (__ballot(valid && (s | nw) != fm)) row_full = false;
-        if (nw) st_prow(&st.seen[u * W + w], s | nw);
+        if (nw) st_row(&st.seen[u * W + w], s | nw);
         // single-slice rows are written only when active; multi-slice rows always (a row
         // must be whole whenever its A bit is set)
-        if (valid && (any || nslices > 1)) st_prow(&Fc[u * W + w], nw);
+        if (valid && (any || nslices > 1)) st_row(&Fc[u * W + w], nw);
         if (nw) {
           const uint64_t pc = (uint64_t)__popcll(nw);
           c[ST_NEW] += pc;
@@ -248,11 +233,7 @@ __device__ __forceinline__ uint64_t src_word_m(const uint64_t* __restrict__ Src,
     const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32),
                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
     // (row is wave-uniform: a 32 x 32 -> 64 scalar product, at_row, instead of an int64 one)
-#if P2PG_NT_LOADS
     x = __builtin_nontemporal_load(at_row(Src, row, W) + pos);
-#else
-    x = at_row(Src, row, W)[pos];
-#endif
   }
   return x;
 }
@@ -269,11 +250,7 @@ __device__ __forceinline__ uint64_t src_word_pair(const uint64_t* __restrict__ S
     const bool lo = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) < 32u;
     const uint32_t pos = __builtin_amdgcn_mbcnt_hi(m1, __builtin_amdgcn_mbcnt_lo(lo ? m0 : 0u, 0u));
     const uint32_t row = lo ? r0 : r1;  // (per lane: a 32 x 32 -> 64 address, at_row)
-#if P2PG_NT_LOADS
     x = __builtin_nontemporal_load(at_row(Src, row, W) + pos);
-#else
-    x = at_row(Src, row, W)[pos];
-#endif
   }
   return x;
 }
@@ -284,11 +261,7 @@ __device__ __forceinline__ uint64_t src_word_pair(const uint64_t* __restrict__ S
 // target t+1's activity gather (A bits of its neighbours) is issued, before target t's rows
 // are loaded, and all three wait together.  Hub targets (g.H) are left to k_pull_hub_*.
 template <bool CHURN, bool GOSSIP>
-#ifndef P2PG_PULL_WAVES
-#define P2PG_PULL_WAVES 1
-#endif
-__global__ __launch_bounds__(256, P2PG_PULL_WAVES) void k_pull1(DevGraph g, DevState st,
-                                                                RoundParams p) {
+__global__ __launch_bounds__(256, 1) void k_pull1(DevGraph g, DevState st, RoundParams p) {
   const int lane = threadIdx.x & 63;
   const int wib = wave_in_block();
   const int64_t V = g.V;
@@ -427,7 +400,7 @@ __global__ __launch_bounds__(256, P2PG_PULL_WAVES) void k_pull1(DevGraph g, DevS
       const uint64_t nw = acc & need;
       const bool any = __ballot(nw != 0ull) != 0ull;
       if (nw) {
-        st_prow(at_row(st.seen, u, W) + lane, s1.s | nw);
+        st_row(at_row(st.seen, u, W) + lane, s1.s | nw);
         const uint64_t pc = (uint64_t)__popcll(nw);
         const uint64_t per_bit = GOSSIP ? (deg < (uint64_t)p.fanout ? deg : (uint64_t)p.fanout)
                                         : deg - 1;
@@ -437,7 +410,7 @@ __global__ __launch_bounds__(256, P2PG_PULL_WAVES) void k_pull1(DevGraph g, DevS
         c[ST_WEDGES] += deg;
       }
       if (any) {
-        if (valid) st_prow(at_row(Fc, u, W) + lane, nw);
+        if (valid) st_row(at_row(Fc, u, W) + lane, nw);
         aw |= 1u << s1.b;
         const uint64_t wm = __ballot(nw != 0ull);
         if (lane == 0) {
@@ -458,86 +431,15 @@ __global__ __launch_bounds__(256, P2PG_PULL_WAVES) void k_pull1(DevGraph g, DevS
   flush_stats(st.stats, c, lane);
 }
 
-// Hub targets of the pull (deg > HUB_T), part 1: one wave per (hub, HUB_CHUNK-slot chunk)
-// ORs that chunk's active source rows into a partial row.
-template <bool CHURN, bool GOSSIP>
-__global__ __launch_bounds__(256) void k_pull_hub_partial(DevGraph g, DevState st,
-                                                          RoundParams p, HubPlan hp) {
-  const int lane = threadIdx.x & 63;
-  const int wib = wave_in_block();
-  const int W = st.W;
-  const int prv = (p.round & 1) ^ 1;
-  const uint64_t* __restrict__ Src = GOSSIP ? st.E[prv] : st.F[prv];
-  const uint32_t* __restrict__ Ap = st.A[prv];
-  const uint64_t* __restrict__ AWp = GOSSIP ? st.AW[prv] : nullptr;
-  const bool packed = GOSSIP && AWp != nullptr;
-  const bool valid = lane < W;
-  const uint64_t fm = valid ? full_mask(lane, W, st.M) : 0ull;
-  for (int64_t it = (int64_t)blockIdx.x * WPB + wib; it < hp.n_items;
-       it += (int64_t)gridDim.x * WPB) {
-    const int64_t item = hp.items[it];
-    const int64_t u = item >> 32;
-    const int64_t chunk = item & 0xFFFFFFFFll;
-    const int64_t rb = g.rowptr[u], re = g.rowptr[u + 1];
-    const int64_t beg = rb + chunk * HUB_CHUNK;
-    const int64_t end = beg + HUB_CHUNK < re ? beg + HUB_CHUNK : re;
-    const uint64_t need = valid ? fm & ~at_row(st.seen, u, W)[lane] : 0ull;
-    uint64_t acc = 0;
-    if (__ballot(need != 0ull) && !bit_test(st.S, u)) {
-      for (int64_t cb = beg; cb < end; cb += 64) {
-        const int64_t j = cb + lane;
-        uint32_t srow = 0;
-        uint64_t sam = 0;
-        bool a = false;
-        if (j < end) {
-          const int32_t v = g.colidx[j];
-          srow = GOSSIP ? (uint32_t)j : (uint32_t)v;
-          a = bit_test(Ap, v);
-          if (CHURN && a)
-            a = !churn_dropped((uint32_t)(p.round - 1), gidx(g, u), gidx(g, v), p.churn_thr,
-                               p.cseed_lo, p.cseed_hi);
-          if (packed && a) sam = AWp[v];
-        }
-        uint64_t m = __ballot(a);
-        while (m) {
-          uint32_t sv[8];
-          uint64_t am[8];
-          bool ok[8];
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            ok[k] = m != 0ull;
-            am[k] = 0ull;
-            if (m) {
-              const int idx = __builtin_ctzll(m);
-              m &= m - 1ull;
-              sv[k] = (uint32_t)__builtin_amdgcn_readlane((int)srow, idx);
-              if (packed) am[k] = (uint64_t)readlane64((int64_t)sam, idx);
-            } else {
-              sv[k] = 0u;
-            }
-          }
-          uint64_t x[8];
-#pragma unroll
-          for (int k = 0; k < 8; ++k)
-            x[k] = src_word(Src, sv[k], W, lane, packed, am[k], ok[k] && need);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) acc |= x[k];
-        }
-      }
-    }
-    hp.partial[it * 64 + lane] = acc;
-  }
-}
-
-// Hub targets, part 2: one wave per hub ORs its partial rows, dedups against seen and writes
-// the frontier row; A / S bits by atomicOr (the main pull kernel stored those words whole).
-// The same partial rows with the hub's adjacency segment staged in LDS (north_star: "LDS-staged
-// high-degree adjacency segments"): one 256-thread block per (hub, HUB_CHUNK-slot) item.  All 256
-// threads load the chunk's neighbour ids, activity (and churn) and packed-word masks at once -- one
-// memory trip for the whole segment instead of one per 64-slot window of a single wave -- and
-// compact the active slots into an LDS list (any order: the rows are ORed); then the 4 waves
+// Hub targets of the pull (deg > HUB_T), part 1: the active source rows of every (hub,
+// HUB_CHUNK-slot chunk) item are ORed into a partial row, with the hub's adjacency segment staged
+// in LDS (north_star: "LDS-staged high-degree adjacency segments"): one 256-thread block per item.
+// All 256 threads load the chunk's neighbour ids, activity (and churn) and packed-word masks at
+// once -- one memory trip for the whole segment instead of one per 64-slot window of a single wave
+// -- and compact the active slots into an LDS list (any order: the rows are ORed); then the 4 waves
 // gather the listed rows (lane = word, 8 in flight) and their ORs are folded through LDS.
-// The default since round 4 (A/B against k_pull_hub_partial).
+// (Against one wave per item, c4 interleaved A/B, profiles/r04/ab_hub_lds.txt: fused rounds
+// 211.8 -> 210.9 ms per step)
 template <bool CHURN, bool GOSSIP>
 __global__ __launch_bounds__(256) void k_pull_hub_lds(DevGraph g, DevState st, RoundParams p,
                                                       HubPlan hp) {
@@ -613,24 +515,16 @@ __global__ __launch_bounds__(256) void k_pull_hub_lds(DevGraph g, DevState st, R
   }
 }
 
-// part 1 of the hub pull: the LDS-staged kernel (c4 interleaved A/B, profiles/r04/ab_hub_lds.txt:
-// fused rounds 211.8 -> 210.9 ms per step); P2PG_HUB_LDS=0 keeps one wave per item
 template <bool CHURN, bool GOSSIP>
 void launch_hub_partial(const DevGraph& g, const DevState& st, const RoundParams& p,
                         const HubPlan& hp, hipStream_t s) {
-  static const bool lds = [] {
-    const char* e = std::getenv("P2PG_HUB_LDS");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  if (lds)
-    hipLaunchKernelGGL((k_pull_hub_lds<CHURN, GOSSIP>),
-                       dim3((unsigned)std::min<int64_t>(hp.n_items, 65535)), dim3(256), 0, s, g, st,
-                       p, hp);
-  else
-    hipLaunchKernelGGL((k_pull_hub_partial<CHURN, GOSSIP>), dim3(grid_tasks(hp.n_items)),
-                       dim3(256), 0, s, g, st, p, hp);
+  hipLaunchKernelGGL((k_pull_hub_lds<CHURN, GOSSIP>),
+                     dim3((unsigned)std::min<int64_t>(hp.n_items, 65535)), dim3(256), 0, s, g, st, p,
+                     hp);
 }
 
+// Hub targets, part 2: one wave per hub ORs its partial rows, dedups against seen and writes
+// the frontier row; A / S bits by atomicOr (the main pull kernel stored those words whole).
 template <bool GOSSIP>
 __global__ __launch_bounds__(256) void k_pull_hub_finalize(DevGraph g, DevState st,
                                                            RoundParams p, HubPlan hp) {
@@ -652,7 +546,7 @@ __global__ __launch_bounds__(256) void k_pull_hub_finalize(DevGraph g, DevState 
     const uint64_t nw = acc & fm & ~s;
     const uint64_t deg = (uint64_t)(g.rowptr[u + 1] - g.rowptr[u]);
     if (nw) {
-      st_prow(at_row(st.seen, u, W) + lane, s | nw);
+      st_row(at_row(st.seen, u, W) + lane, s | nw);
       const uint64_t pc = (uint64_t)__popcll(nw);
       const uint64_t per_bit = GOSSIP ? (deg < (uint64_t)p.fanout ? deg : (uint64_t)p.fanout)
                                       : deg - 1;
@@ -662,7 +556,7 @@ __global__ __launch_bounds__(256) void k_pull_hub_finalize(DevGraph g, DevState 
       c[ST_WEDGES] += deg;
     }
     if (__ballot(nw != 0ull)) {
-      if (valid) st_prow(&st.F[cur][u * W + lane], nw);
+      if (valid) st_row(&st.F[cur][u * W + lane], nw);
       const uint64_t wm = __ballot(nw != 0ull);
       if (lane == 0) {
         if (GOSSIP && st.AW[cur]) st.AW[cur][u] = wm;
@@ -716,7 +610,7 @@ __global__ __launch_bounds__(256) void k_gossip_update(DevGraph g, DevState st,
         if (valid) {
           x = nx[u * W + w];
           if (x) {
-            st_prow(&nx[u * W + w], 0ull);
+            st_row(&nx[u * W + w], 0ull);
             s = st.seen[u * W + w];
             c[ST_AUX] += 1;  // touched (pushed-to) words consumed
           }
@@ -726,8 +620,8 @@ __global__ __launch_bounds__(256) void k_gossip_update(DevGraph g, DevState st,
         const bool any = wm != 0ull;
         row_new |= any;
         if (any && nslices == 1 && st.AW[cur] && lane == 0) st.AW[cur][u] = wm;
-        if (nw) st_prow(&st.seen[u * W + w], s | nw);
-        if (valid && (any || nslices > 1)) st_prow(&Fc[u * W + w], nw);
+        if (nw) st_row(&st.seen[u * W + w], s | nw);
+        if (valid && (any || nslices > 1)) st_row(&Fc[u * W + w], nw);
         if (nw) {
           const uint64_t pc = (uint64_t)__popcll(nw);
           c[ST_NEW] += pc;
@@ -859,14 +753,14 @@ __global__ __launch_bounds__(256) void k_gossip_update1(DevGraph g, DevState st,
     const uint64_t fan = p.mode == 0 ? (uint64_t)(deg > 0 ? deg - 1 : 0)
                                      : (uint64_t)(deg < p.fanout ? deg : p.fanout);
     if (x) {
-      st_prow(at_row(nx, u, W) + wl, 0ull);
+      st_row(at_row(nx, u, W) + wl, 0ull);
       c[ST_AUX] += 1;  // touched (pushed-to) words consumed
     }
     const uint64_t nw = x & ~s;
     const uint64_t wm = PAIR ? (wm_all >> shift) & 0xFFFFFFFFull : wm_all;
     if (wm && st.AW[cur] && wl == 0) st.AW[cur][u] = wm;
-    if (nw) st_prow(at_row(st.seen, u, W) + wl, s | nw);
-    if (valid && wm && (p.store_f != 2 || nw)) st_prow(at_row(Fc, u, W) + wl, nw);  // (2: AW-valid rows)
+    if (nw) st_row(at_row(st.seen, u, W) + wl, s | nw);
+    if (valid && wm && (p.store_f != 2 || nw)) st_row(at_row(Fc, u, W) + wl, nw);  // (2: AW-valid rows)
     if (nw) {
       const uint64_t pc = (uint64_t)__popcll(nw);
       c[ST_NEW] += pc;
@@ -970,13 +864,13 @@ __global__ __launch_bounds__(256) void k_gossip_update_g(DevGraph g, DevState st
       if (ok) x = at_row(nx, u, W)[w];
       if (x) {
         s = at_row(st.seen, u, W)[w];
-        st_prow(at_row(nx, u, W) + w, 0ull);
+        st_row(at_row(nx, u, W) + w, 0ull);
         c[ST_AUX] += 1;  // touched (pushed-to) words consumed
       }
       const uint64_t nw = x & ~s;
       const uint64_t wm = (__ballot(nw != 0ull) >> (grp * WP)) & segm;  // this peer's new words
-      if (nw) st_prow(at_row(st.seen, u, W) + w, s | nw);
-      if (ok && wm) st_prow(at_row(Fc, u, W) + w, nw);
+      if (nw) st_row(at_row(st.seen, u, W) + w, s | nw);
+      if (ok && wm) st_row(at_row(Fc, u, W) + w, nw);
       if (wm) {
         const int64_t deg = g.rowptr[u + 1] - g.rowptr[u];
         // relays per first receipt: gossip min(k, deg); flood (rows materialized by a topology
@@ -1084,13 +978,13 @@ __global__ __launch_bounds__(256) void k_gossip_update_gp(DevGraph g, DevState s
     const int64_t u = q.me;
     const uint64_t x = q.x, s = q.s;
     if (x) {
-      st_prow(at_row(nx, u, W) + w, 0ull);
+      st_row(at_row(nx, u, W) + w, 0ull);
       c[ST_AUX] += 1;  // touched (pushed-to) words consumed
     }
     const uint64_t nw = x & ~s;
     const uint64_t wm = (__ballot(nw != 0ull) >> (grp * WP)) & segm;  // this peer's new words
-    if (nw) st_prow(at_row(st.seen, u, W) + w, s | nw);
-    if (q.me >= 0 && wvalid && wm) st_prow(at_row(Fc, u, W) + w, nw);
+    if (nw) st_row(at_row(st.seen, u, W) + w, s | nw);
+    if (q.me >= 0 && wvalid && wm) st_row(at_row(Fc, u, W) + w, nw);
     uint32_t bit = 0;
     if (wm) {
       const int64_t deg = (int64_t)(q.r1 - q.r0);
@@ -1212,22 +1106,12 @@ __global__ __launch_bounds__(256) void k_materialize(DevGraph g, DevState st, Ro
 #define PROF_PASS
 #endif
 
-#ifndef P2PG_PICK_PAIRS
-#define P2PG_PICK_PAIRS 0
-#endif
-#ifndef P2PG_COMPACT
-#define P2PG_COMPACT 1
-#endif
-
 // LDS of one scatter wave: a GCHUNK x 64-word mask table (two 32-bit halves per word, so
 // 32-bit LDS atomics) and the compacted list of active (word, bit) entries.
-// Half-major rows (P2PG_TBL_HALF_MAJOR, default): connection j's row is [half][word], so the
+// Half-major rows: connection j's row is [half][word], so the
 // 64 lanes of a pick batch -- entries of ~64 different words -- OR into 64 different banks;
 // with the halves adjacent ([word][half], a 64-bit LDS access per mask) words w and w+32 share
 // a bank (2-way conflicts: 40-49 % of the fused kernel's LDS cycles, profiles/r01/pmc_sq_v11).
-#ifndef P2PG_TBL_HALF_MAJOR
-#define P2PG_TBL_HALF_MAJOR 1
-#endif
 struct ScatterLds {
   alignas(8) uint32_t tbl[GCHUNK * 128];
   uint16_t lst[GLIST];
@@ -1235,11 +1119,7 @@ struct ScatterLds {
 
 // u32 index of half h of (connection j, word w)
 __device__ __forceinline__ uint32_t tbl_ix(uint32_t j, uint32_t w, uint32_t h) {
-#if P2PG_TBL_HALF_MAJOR
   return j * 128u + h * 64u + w;
-#else
-  return j * 128u + w * 2u + h;
-#endif
 }
 
 // u32 index of list entry e = word << 6 | bit in connection 0's row
@@ -1248,11 +1128,7 @@ __device__ __forceinline__ uint32_t tbl_entry_ix(uint32_t e) {
 }
 
 __device__ __forceinline__ uint64_t tbl_word(const ScatterLds& L, int j, int w) {
-#if P2PG_TBL_HALF_MAJOR
   return ((uint64_t)L.tbl[tbl_ix(j, w, 1)] << 32) | L.tbl[tbl_ix(j, w, 0)];
-#else
-  return *reinterpret_cast<const uint64_t*>(&L.tbl[tbl_ix(j, w, 0)]);
-#endif
 }
 
 __device__ __forceinline__ void tbl_clear(ScatterLds& L, int j, int w) {
@@ -1265,8 +1141,7 @@ __device__ __forceinline__ void tbl_clear(ScatterLds& L, int j, int w) {
 //   1. the row slice's active bits are compacted into an LDS list (prefix sum of popcounts),
 //      so the 64 lanes evaluate Philox + Floyd for equal shares of messages;
 //   2. picks landing in the chunk set bits of a GCHUNK x 64-word LDS mask table (32-bit LDS
-//      atomics; table = [target][word][half]: one 64-bit LDS access per (target, word) in the
-//      clear and the flush);
+//      atomics; table = [target][half][word], see ScatterLds);
 //   3. flush, lane = word: every (target, word) mask leaves as part of one 512 B row access --
 //      STORE_E = false (sparse rounds): row atomicOr into the target's next row + T bit;
 //      STORE_E = true  (dense rounds):  plain store of the whole row (zeros included) into
@@ -1315,7 +1190,7 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
     uint32_t* const col = &L.tbl[tbl_entry_ix(e)];  // connection 0's (word, half)
     const uint32_t mb = ok ? 1u << (bit & 31u) : 0u;
     uint32_t pk[K > 0 ? K : 1];
-    if constexpr (P2PG_PICK_FOLD && K > 0 && K <= 4)
+    if constexpr (K > 0 && K <= 4)
       gossip_picks_k<K>(pkey, mg, (uint32_t)deg, pk);
     else
       gossip_picks_t<(K > 0 ? K : 1)>((uint32_t)p.round, gv, mg, (uint32_t)deg, p.gseed_lo,
@@ -1335,18 +1210,6 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
     const uint32_t nbat = (n + 63) >> 6;
     const uint32_t i0 = (uint32_t)lane * nbat;
     const uint32_t cnt = i0 < n ? (n - i0 < nbat ? n - i0 : nbat) : 0u;
-#if P2PG_PICK_PAIRS
-    // two entries per iteration, evaluated unconditionally (the second's atomics masked when
-    // past the lane's share): two independent Philox chains interleave and hide each other's
-    // multiply latency
-    for (uint32_t b = 0; b < cnt; b += 2) {
-      const uint32_t e0 = L.lst[i0 + b];
-      const bool two = b + 1 < cnt;
-      const uint32_t e1 = two ? L.lst[i0 + b + 1] : e0;
-      one(check_v, e0, true);
-      one(check_v, e1, two);
-    }
-#else
     // Uniform trip count: a lane past its share evaluates a dummy entry whose table ORs carry
     // an empty mask, so the loop needs no per-lane exit bookkeeping.  i0 + b + 1 <= GLIST.
     uint32_t en = L.lst[i0];
@@ -1356,7 +1219,6 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
       en = L.lst[ni < (uint32_t)GLIST ? ni : (uint32_t)GLIST - 1u];
       one(check_v, e, b < cnt);
     }
-#endif
   };
 
   // Compact table clear and flush (few active words, no churn): the nf <= 32 active words of
@@ -1365,7 +1227,7 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
   // connections instead of one (light dense rounds: ~8 active words, 4 connections at once).
   // The picks touch only the active words' table columns, so only those are cleared.
   const int nf = __popcll(fam);
-  const bool compact = P2PG_COMPACT && !CHURN && anyf && nf <= 32 &&
+  const bool compact = !CHURN && anyf && nf <= 32 &&
                        (STORE_E ? st.AW[cur] != nullptr : g.gone == nullptr);
   const bool use_tbl = anyf && !all;
   int seg = 64, rk_lane = 0, wc = 0, gl = 0;
@@ -1397,9 +1259,12 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
     const uint32_t cnt = (uint32_t)__popcll(f);
     // at most one new bit per word (light rounds: ~9 bits in ~8 words per peer): lane w's word
     // is its own entry, one Philox batch with no list (the scan, the list writes and a sync cost
-    // more than the batch itself there)
+    // more than the batch itself there).  DIRECT: taken by the fused kernel's first-dense-round
+    // modes (push-only, update + push): c4 round 10 7.4 -> 6.9 ms; in the fused rounds proper the
+    // extra path cost more in the peak rounds than it saved in the light ones (211.2 -> 211.9 ms
+    // per step, profiles/r06/ab_pick_direct.txt)
     bool direct = false;
-    if constexpr (DIRECT && K > 0 && P2PG_PICK_DIRECT) {
+    if constexpr (DIRECT && K > 0) {
       direct = __ballot(cnt > 1u) == 0ull;
       if (direct) {
         wave_lds_sync();  // (the table clear above, before the table atomics)
@@ -1620,7 +1485,7 @@ __device__ __forceinline__ void scatter_wide(const DevGraph& g, const DevState& 
           uint32_t* const col = &L.tbl[rr * 2u + (bit >> 5)];
           const uint32_t mb = b < mine ? 1u << (bit & 31u) : 0u;
           uint32_t pk[K];
-          if constexpr (P2PG_PICK_FOLD && K <= 4)
+          if constexpr (K <= 4)
             gossip_picks_k<K>(pkey, mg, deg, pk);
           else
             gossip_picks_t<K>((uint32_t)p.round, gv, mg, deg, p.gseed_lo, p.gseed_hi, pk);
@@ -1789,12 +1654,7 @@ __global__ __launch_bounds__(256) void k_gossip_scatter(DevGraph g, DevState st,
 }
 
 // Active neighbours whose E words the fused kernel keeps in flight across a target's picks.
-#ifndef P2PG_FG
-#define P2PG_FG 8
-#endif
-constexpr int FG = P2PG_FG;
-
-
+constexpr int FG = 8;
 
 // Gossip dense round r >= 1 after a dense round r-1: the pull of round r (k_pull1<false,
 // true>: arrivals = packed E[(r-1)&1] rows of the active neighbours) and, for every peer with
@@ -1808,9 +1668,7 @@ constexpr int FG = P2PG_FG;
 // resident per SIMD; the looser bound only changes the compiler's schedule, which measured
 // 1.3-1.4 ms per c4 step faster on two boxes (2: no better; W = 32 / 16 shares equal,
 // profiles/r04/ab_fused_waves.txt)
-#ifndef P2PG_FUSED_WAVES
-#define P2PG_FUSED_WAVES 3
-#endif
+constexpr int FUSED_WAVES = 3;
 // MODE 0: the fused dense round above.
 // MODE 1, PO (push only): the first dense round after an update (16 < W <= 64, packed E) -- the
 // peers are the round's active non-hub peers, their arrivals are their own frontier rows F[r&1]
@@ -1831,8 +1689,8 @@ constexpr int FG = P2PG_FG;
 // arrivals here), pushes to ghosts go to their row pushes (scatter_row PART), Philox ids are
 // global (gid).  The caller clears the consumed row pushes afterwards (launch_clear_arrivals).
 template <bool CHURN, int K, int MODE = 0, bool HALF = false, bool PART = false>
-__global__ __launch_bounds__(256, P2PG_FUSED_WAVES) void k_gossip_fused(DevGraph g, DevState st,
-                                                                        RoundParams p) {
+__global__ __launch_bounds__(256, FUSED_WAVES) void k_gossip_fused(DevGraph g, DevState st,
+                                                                   RoundParams p) {
   constexpr bool PO = MODE == 1, UP = MODE == 2, PL = MODE == 3;
   constexpr bool GATHER = MODE == 0 || PL;  // arrivals gathered from E
   static_assert(!(PART && UP), "no update+push pass on partitioned ranks");
@@ -1921,15 +1779,15 @@ __global__ __launch_bounds__(256, P2PG_FUSED_WAVES) void k_gossip_fused(DevGraph
     if (q.u < 0) return;
     // PO: the peer's frontier row (its new receipts of this round) instead of its seen row;
     // UP: the seen row and, in the stage's mask field, the push row (the arrivals)
-    if (valid) q.s = ld_once(at_row(PO ? Fc : st.seen, q.u, W) + lane);
+    if (valid) q.s = at_row(PO ? Fc : st.seen, q.u, W)[lane];
     if (UP) q.am = valid ? at_row(st.next[cur], q.u, W)[lane] : 0ull;
     // PO: the row's active-word mask (a frontier row written by the update may hold stale words
     // outside it, RoundParams::store_f == 2)
     if (PO) q.am = ldc(st.AW[cur] + q.u);
     const uint32_t j = q.beg + lane;
     if (j < q.end) {
-      if (GATHER) q.v = ld_once(&g.colidx[j]);
-      if (!PL || PART) q.rv = ld_once(&g.rev[j]);  // (PART: ghost marks)
+      if (GATHER) q.v = g.colidx[j];
+      if (!PL || PART) q.rv = g.rev[j];  // (PART: ghost marks)
     }
   };
   // loads only; gather() tests the bit (see k_pull1)
@@ -2085,7 +1943,7 @@ __global__ __launch_bounds__(256, P2PG_FUSED_WAVES) void k_gossip_fused(DevGraph
     // the wait below covers them
     uint64_t remote = 0;
     if (PART && GATHER && ((ldc(st.T[cur] + (u >> 5)) >> (u & 31)) & 1u) && valid)
-      remote = ld_once(at_row(st.next[cur], u, W) + lane);
+      remote = at_row(st.next[cur], u, W)[lane];
     PROF_MARK(0);
     if (GATHER) {
       uint64_t m = a.mr;  // the rest of the first 64 slots, then further 64-slot chunks
@@ -2163,7 +2021,7 @@ __global__ __launch_bounds__(256, P2PG_FUSED_WAVES) void k_gossip_fused(DevGraph
     if (HALF) acc |= bperm64(lane ^ 32, acc);  // lanes 32-63 gathered for words 0-31 too
     if (PART) acc |= remote;
     if (UP && acc) {  // the push row is consumed: all-zero again outside touched rows
-      st_prow(at_row(st.next[cur], u, W) + lane, 0ull);
+      st_row(at_row(st.next[cur], u, W) + lane, 0ull);
       c[ST_AUX] += 1;  // touched (pushed-to) words consumed
     }
     flush_pending();
@@ -2176,7 +2034,7 @@ __global__ __launch_bounds__(256, P2PG_FUSED_WAVES) void k_gossip_fused(DevGraph
     const uint64_t nw = PO ? ((a.am >> lane) & 1ull ? a.s : 0ull) : acc & need;
     const uint64_t wm = __ballot(nw != 0ull);
     if (!PO && nw) {
-      st_frow(at_row(st.seen, u, W) + lane, a.s | nw);
+      st_row(at_row(st.seen, u, W) + lane, a.s | nw);
       const uint32_t pc = (uint32_t)__popcll(nw);
       const uint32_t kf = K > 0 ? (uint32_t)K : (uint32_t)p.fanout;
       const uint32_t per_bit = deg < (uint64_t)kf ? (uint32_t)deg : kf;
@@ -2187,7 +2045,7 @@ __global__ __launch_bounds__(256, P2PG_FUSED_WAVES) void k_gossip_fused(DevGraph
     }
     if (wm) {
       if (!PO) {
-        if (valid && p.store_f && (p.store_f != 2 || nw)) st_frow(at_row(Fc, u, W) + lane, nw);
+        if (valid && p.store_f && (p.store_f != 2 || nw)) st_row(at_row(Fc, u, W) + lane, nw);
         aw |= 1u << (u & 31);
         if (lane == 0) {
           st.AW[cur][u] = wm;
@@ -2526,6 +2384,33 @@ __global__ void k_philox(int32_t n, const uint32_t* ctr, uint32_t k0, uint32_t k
 
 }  // namespace
 
+// After a PART gather round: the exchanged row pushes it consumed (next[r&1] rows with a T bit,
+// saturated peers' included) are cleared, so the plane is all-zero outside pending pushes again.
+// One wave per 64 bitmap words (lane = word), then lane = row word per set bit.
+__global__ __launch_bounds__(256) void k_clear_arrivals(DevState st, int32_t round, int64_t nwords) {
+  const int lane = threadIdx.x & 63;
+  const int W = st.W;
+  const int cur = round & 1;
+  uint32_t* __restrict__ T = st.T[cur];
+  uint64_t* __restrict__ nx = st.next[cur];
+  for (int64_t base = ((int64_t)blockIdx.x * WPB + wave_in_block()) * 64; base < nwords;
+       base += (int64_t)gridDim.x * WPB * 64) {
+    const int64_t i = base + lane;
+    const uint32_t t = i < nwords ? T[i] : 0u;
+    if (t) T[i] = 0u;
+    for (uint64_t m = __ballot(t != 0u); m; m &= m - 1ull) {
+      const int l = __builtin_ctzll(m);
+      uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)t, l);
+      const int64_t w0 = (base + l) << 5;
+      while (b) {
+        const int64_t u = w0 + __builtin_ctz(b);
+        b &= b - 1u;
+        if (lane < W) nx[u * W + lane] = 0ull;
+      }
+    }
+  }
+}
+
 hipError_t launch_zero_rows(uint64_t* plane, int32_t W, const int32_t* rows, int32_t n,
                             hipStream_t s) {
   const int64_t tot = (int64_t)n * W;
@@ -2569,18 +2454,20 @@ hipError_t launch_flood_pull(const DevGraph& g, const DevState& st, const RoundP
                      : pull_with_hubs<false, false>(g, st, p, hp, s);
 }
 
-// k_gossip_fused by churn / fanout (MODE 0, PART) and width (HALF: W <= 32)
-template <bool CH, int KK, int MODE, bool PART>
-static void fused_launch(bool half, const DevGraph& g, const DevState& st, const RoundParams& p,
-                         hipStream_t s) {
-  if (half)
-    hipLaunchKernelGGL((k_gossip_fused<CH, KK, MODE, true, PART>),
-                       dim3(balanced_grid(k_gossip_fused<CH, KK, MODE, true, PART>, (g.V + 31) >> 5)),
-                       dim3(256), 0, s, g, st, p);
+// One launch of k_gossip_fused<CH, K, MODE, HALF, PART> on its balanced grid.
+template <bool CH, int K, int MODE = 0, bool HALF = false, bool PART = false>
+static void fused_launch(const DevGraph& g, const DevState& st, const RoundParams& p, hipStream_t s) {
+  const auto kernel = k_gossip_fused<CH, K, MODE, HALF, PART>;
+  hipLaunchKernelGGL(kernel, dim3(balanced_grid(kernel, (g.V + 31) >> 5)), dim3(256), 0, s, g, st, p);
+}
+
+// ... by width: rows of W <= 32 words gather two slots per load (HALF)
+template <bool CH, int K, int MODE, bool PART = false>
+static void fused_launch_w(const DevGraph& g, const DevState& st, const RoundParams& p, hipStream_t s) {
+  if (st.W <= 32)
+    fused_launch<CH, K, MODE, true, PART>(g, st, p, s);
   else
-    hipLaunchKernelGGL((k_gossip_fused<CH, KK, MODE, false, PART>),
-                       dim3(balanced_grid(k_gossip_fused<CH, KK, MODE, false, PART>, (g.V + 31) >> 5)),
-                       dim3(256), 0, s, g, st, p);
+    fused_launch<CH, K, MODE, false, PART>(g, st, p, s);
 }
 
 // Partitioned ranks (PART, see internal.h): no hub split (H = nullptr: every peer, hubs included,
@@ -2595,73 +2482,26 @@ static hipError_t launch_gossip_fused_part(const DevGraph& g, const DevState& st
   if (!part_launch_ok(g, st, (p.round & 1) ^ 1) || p.phase >= 0) return hipErrorInvalidValue;
   DevGraph g2 = g;
   g2.H = nullptr;
-  const bool half = st.W <= 32;
-  const bool ch = p.churn_thr != 0;
-  switch (p.fanout) {
-    case 1: ch ? fused_launch<true, 1, 0, true>(half, g2, st, p, s) : fused_launch<false, 1, 0, true>(half, g2, st, p, s); break;
-    case 2: ch ? fused_launch<true, 2, 0, true>(half, g2, st, p, s) : fused_launch<false, 2, 0, true>(half, g2, st, p, s); break;
-    case 3: ch ? fused_launch<true, 3, 0, true>(half, g2, st, p, s) : fused_launch<false, 3, 0, true>(half, g2, st, p, s); break;
-    case 4: ch ? fused_launch<true, 4, 0, true>(half, g2, st, p, s) : fused_launch<false, 4, 0, true>(half, g2, st, p, s); break;
-    default: ch ? fused_launch<true, 0, 0, true>(half, g2, st, p, s) : fused_launch<false, 0, 0, true>(half, g2, st, p, s); break;
-  }
+  dispatch_fanout_churn(p, [&](auto ch, auto k) {
+    fused_launch_w<decltype(ch)::value, decltype(k)::value, 0, true>(g2, st, p, s);
+  });
   return hipGetLastError();
-}
-
-// After a PART gather round: the exchanged row pushes it consumed (next[r&1] rows with a T bit,
-// saturated peers' included) are cleared, so the plane is all-zero outside pending pushes again.
-// One wave per 64 bitmap words (lane = word), then lane = row word per set bit.
-__global__ __launch_bounds__(256) void k_clear_arrivals(DevState st, int32_t round, int64_t nwords) {
-  const int lane = threadIdx.x & 63;
-  const int W = st.W;
-  const int cur = round & 1;
-  uint32_t* __restrict__ T = st.T[cur];
-  uint64_t* __restrict__ nx = st.next[cur];
-  for (int64_t base = ((int64_t)blockIdx.x * WPB + wave_in_block()) * 64; base < nwords;
-       base += (int64_t)gridDim.x * WPB * 64) {
-    const int64_t i = base + lane;
-    const uint32_t t = i < nwords ? T[i] : 0u;
-    if (t) T[i] = 0u;
-    for (uint64_t m = __ballot(t != 0u); m; m &= m - 1ull) {
-      const int l = __builtin_ctzll(m);
-      uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)t, l);
-      const int64_t w0 = (base + l) << 5;
-      while (b) {
-        const int64_t u = w0 + __builtin_ctz(b);
-        b &= b - 1u;
-        if (lane < W) nx[u * W + lane] = 0ull;
-      }
-    }
-  }
-}
-
-static bool grouped_enabled();
-static bool grouped_pull_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("P2PG_GROUPED_PULL");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  return on;
 }
 
 hipError_t launch_gossip_pull(const DevGraph& g, const DevState& st, const RoundParams& p,
                               const HubPlan& hp, hipStream_t s) {
-  // packed rows (8 < W <= 64): the pull-only mode of the fused kernel (its pipeline crosses task
-  // boundaries; W <= 32: two slots per gather load); P2PG_FUSED_PULL=0 keeps the grouped pull-only
-  // kernel (W <= 32) / k_pull1 (A/B only)
-  static const bool fused_pull = [] {
-    const char* e = std::getenv("P2PG_FUSED_PULL");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
   if (g.gid && p.phase < 0) {  // partitioned ranks: the PART pull-only pass, hubs inline
     if (!part_launch_ok(g, st, (p.round & 1) ^ 1)) return hipErrorInvalidValue;
     DevGraph g2 = g;
     g2.H = nullptr;
     RoundParams pp = p;
     pp.store_f = 1;
-    fused_launch<false, 0, 3, true>(st.W <= 32, g2, st, pp, s);
+    fused_launch_w<false, 0, 3, true>(g2, st, pp, s);
     return hipGetLastError();
   }
-  if (fused_pull && st.W <= 64 && st.AW[(p.round & 1) ^ 1] && p.phase < 0) {
+  // packed rows (8 < W <= 64): the pull-only mode of the fused kernel (its pipeline crosses task
+  // boundaries; W <= 32: two slots per gather load)
+  if (st.W <= 64 && st.AW[(p.round & 1) ^ 1] && p.phase < 0) {
     RoundParams pp = p;
     // the sparse push of this round reads the frontier rows (its listed words only: whole rows,
     // or the nonzero words when nobody else can observe them, store_f == 2)
@@ -2669,14 +2509,7 @@ hipError_t launch_gossip_pull(const DevGraph& g, const DevState& st, const Round
     // (K = 0: no picks here, and the relay counters take the run's fanout)
     if (hp.n_items)
       launch_hub_partial<false, true>(g, st, pp, hp, s);
-    if (st.W <= 32)
-      hipLaunchKernelGGL((k_gossip_fused<false, 0, 3, true>),
-                         dim3(balanced_grid(k_gossip_fused<false, 0, 3, true>, (g.V + 31) >> 5)),
-                         dim3(256), 0, s, g, st, pp);
-    else
-      hipLaunchKernelGGL((k_gossip_fused<false, 0, 3>),
-                         dim3(balanced_grid(k_gossip_fused<false, 0, 3>, (g.V + 31) >> 5)),
-                         dim3(256), 0, s, g, st, pp);
+    fused_launch_w<false, 0, 3>(g, st, pp, s);
     if (hp.n_hubs)
       hipLaunchKernelGGL((k_pull_hub_finalize<true>), dim3(grid_tasks(hp.n_hubs)), dim3(256), 0,
                          s, g, st, pp, hp);
@@ -2684,7 +2517,7 @@ hipError_t launch_gossip_pull(const DevGraph& g, const DevState& st, const Round
   }
   // narrow rows: several peers per wave (the grouped fused kernel without its pushes); the hubs
   // are left to the hub items as in the fused rounds
-  if (grouped_enabled() && grouped_pull_enabled() && st.W <= GROUPED_PULL_W_MAX && p.phase < 0) {
+  if (st.W <= GROUPED_PULL_W_MAX && p.phase < 0) {
     if (hp.n_items)
       launch_hub_partial<false, true>(g, st, p, hp, s);
     hipError_t r = launch_gossip_pull_grouped(g, st, p, s);
@@ -2707,73 +2540,31 @@ hipError_t launch_materialize(const DevGraph& g, const DevState& st, const Round
   return hipGetLastError();
 }
 
-// W <= 32 rows: two touched peers per stage of the pipelined update (P2PG_UPDATE_PAIR=0: one)
-static bool update_pair_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("P2PG_UPDATE_PAIR");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  return on;
-}
-
-// 32 < W <= 64 rows: two touched peers per stage of the pipelined update (P2PG_UPDATE_DUAL=0: one)
-static bool update_dual_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("P2PG_UPDATE_DUAL");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  return on;
-}
+// blocks cap of the update: c4 A/B, interleaved, update ms per step: 256 / 512 / 1024 /
+// 2048 (GRID_MAX) / 4096 / 8192 blocks -> 40.8 / 25.7 / 18.25 / 18.7 / 20.0 / 22.9
+constexpr int64_t UPDATE_GRID_CAP = 1024;
 
 hipError_t launch_gossip_update(const DevGraph& g, const DevState& st, const RoundParams& p,
                                 hipStream_t s) {
-  // blocks cap (P2PG_UPDATE_GRID): c4 A/B, interleaved, update ms per step: 256 / 512 / 1024 /
-  // 2048 (GRID_MAX) / 4096 / 8192 blocks -> 40.8 / 25.7 / 18.25 / 18.7 / 20.0 / 22.9
-  static const int64_t cap = [] {
-    const char* e = std::getenv("P2PG_UPDATE_GRID");
-    const int64_t v = e ? std::atoll(e) : 1024;
-    return v > 0 ? v : (int64_t)1024;
-  }();
-  const int grid = (int)std::min<int64_t>(grid_tasks((g.V + 31) >> 5), cap);
-  static const bool pipelined = [] {  // P2PG_UPDATE1=0: the unpipelined kernel (A/B only)
-    const char* e = std::getenv("P2PG_UPDATE1");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  static const bool narrow = [] {  // P2PG_UPDATE_G=0: one peer per wave at W <= 32 too (A/B)
-    const char* e = std::getenv("P2PG_UPDATE_G");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  // several touched peers per wave up to W = 16; at W = 32 (two per wave) the pipelined
-  // one-peer kernel is faster (c4 --msgs 2048, profiles/r03/ab_update_g.txt: 20.4 vs 19.65 ms;
-  // W = 16: 10.25 vs 13.95 ms, W = 8: 6.75 vs 12.1 ms)
-  static const bool gp = [] {  // P2PG_UPDATE_GP=0: the unpipelined grouped update at W <= 16 (A/B)
-    const char* e = std::getenv("P2PG_UPDATE_GP");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  if (narrow && gp && st.W > 4 && st.W <= 16) {
-    if (st.W <= 8)
-      hipLaunchKernelGGL(k_gossip_update_gp<3>, dim3(grid), dim3(256), 0, s, g, st, p);
-    else
-      hipLaunchKernelGGL(k_gossip_update_gp<4>, dim3(grid), dim3(256), 0, s, g, st, p);
-  } else if (narrow && st.W <= 16) {
-    int lw = 0;
-    while ((1 << lw) < st.W) ++lw;
-    switch (lw) {
-      case 0: hipLaunchKernelGGL(k_gossip_update_g<0>, dim3(grid), dim3(256), 0, s, g, st, p); break;
-      case 1: hipLaunchKernelGGL(k_gossip_update_g<1>, dim3(grid), dim3(256), 0, s, g, st, p); break;
-      case 2: hipLaunchKernelGGL(k_gossip_update_g<2>, dim3(grid), dim3(256), 0, s, g, st, p); break;
-      case 3: hipLaunchKernelGGL(k_gossip_update_g<3>, dim3(grid), dim3(256), 0, s, g, st, p); break;
-      case 4: hipLaunchKernelGGL(k_gossip_update_g<4>, dim3(grid), dim3(256), 0, s, g, st, p); break;
-      default: hipLaunchKernelGGL(k_gossip_update_g<5>, dim3(grid), dim3(256), 0, s, g, st, p); break;
-    }
-  } else if (st.W <= 32 && pipelined && update_pair_on()) {
+  const int grid = (int)std::min<int64_t>(grid_tasks((g.V + 31) >> 5), UPDATE_GRID_CAP);
+  // several touched peers per wave up to W = 16 (pipelined from W = 5 on); at W = 32 (two per
+  // wave) the pipelined one-peer kernel is faster (c4 --msgs 2048, profiles/r03/ab_update_g.txt:
+  // 20.4 vs 19.65 ms; W = 16: 10.25 vs 13.95 ms, W = 8: 6.75 vs 12.1 ms)
+  if (st.W <= 16) {
+    dispatch_log_width(log2_ceil(st.W), [&](auto lwc) {
+      constexpr int LW = decltype(lwc)::value;
+      if constexpr (LW <= 2)
+        hipLaunchKernelGGL(k_gossip_update_g<LW>, dim3(grid), dim3(256), 0, s, g, st, p);
+      else if constexpr (LW <= 4)
+        hipLaunchKernelGGL(k_gossip_update_gp<LW>, dim3(grid), dim3(256), 0, s, g, st, p);
+    });
+  } else if (st.W <= 32) {  // two touched peers per stage of the pipelined update, half a wave each
     hipLaunchKernelGGL(k_gossip_update1<2>, dim3(grid), dim3(256), 0, s, g, st, p);
-  } else if (st.W <= 64 && pipelined && update_dual_on()) {
+  } else if (st.W <= 64) {  // two touched peers per stage, lane = word of both
     hipLaunchKernelGGL(k_gossip_update1<3>, dim3(grid), dim3(256), 0, s, g, st, p);
-  } else if (st.W <= 64 && pipelined)
-    hipLaunchKernelGGL(k_gossip_update1<1>, dim3(grid), dim3(256), 0, s, g, st, p);
-  else
+  } else {
     hipLaunchKernelGGL(k_gossip_update, dim3(grid), dim3(256), 0, s, g, st, p);
+  }
   return hipGetLastError();
 }
 
@@ -2783,27 +2574,17 @@ void scatter_dispatch(int grid, const DevGraph& g, const DevState& st, const Rou
                       hipStream_t s) {
   // (partitioned ranks' E stores: ghost connections go to row pushes, scatter_row PART)
   const bool part = SE && g.gid != nullptr;
-#define P2PG_SCATTER(CH, KK)                                                                   \
-  do {                                                                                         \
-    if (part)                                                                                  \
-      hipLaunchKernelGGL((k_gossip_scatter<CH, KK, SE, true>), dim3(grid), dim3(256), 0, s, g, \
-                         st, p, hub_items, n_hub_items, task0);                                \
-    else                                                                                       \
-      hipLaunchKernelGGL((k_gossip_scatter<CH, KK, SE>), dim3(grid), dim3(256), 0, s, g, st,   \
-                         p, hub_items, n_hub_items, task0);                                    \
-  } while (0)
-  const bool ch = p.churn_thr != 0;
-  switch (p.fanout) {
-    case 1: if (ch) P2PG_SCATTER(true, 1); else P2PG_SCATTER(false, 1); break;
-    case 2: if (ch) P2PG_SCATTER(true, 2); else P2PG_SCATTER(false, 2); break;
-    case 3: if (ch) P2PG_SCATTER(true, 3); else P2PG_SCATTER(false, 3); break;
-    case 4: if (ch) P2PG_SCATTER(true, 4); else P2PG_SCATTER(false, 4); break;
-    default: if (ch) P2PG_SCATTER(true, 0); else P2PG_SCATTER(false, 0); break;
-  }
-#undef P2PG_SCATTER
+  dispatch_fanout_churn(p, [&](auto ch, auto k) {
+    constexpr bool CH = decltype(ch)::value;
+    constexpr int K = decltype(k)::value;
+    if (part)
+      hipLaunchKernelGGL((k_gossip_scatter<CH, K, SE, true>), dim3(grid), dim3(256), 0, s, g, st, p,
+                         hub_items, n_hub_items, task0);
+    else
+      hipLaunchKernelGGL((k_gossip_scatter<CH, K, SE>), dim3(grid), dim3(256), 0, s, g, st, p,
+                         hub_items, n_hub_items, task0);
+  });
 }
-
-static bool grouped_enabled();
 
 // The push modes of the fused / grouped kernels (push-only, update+push) skip the pull hubs
 // (g.H: deg > HUB_T) and leave their pushes to launch_wide_push_e over wide_big (the same deg >
@@ -2814,24 +2595,17 @@ static bool hub_pushes_ready(const DevGraph& g, const int64_t* big_items, int64_
   return (n_big == 0 || (big_items && wide_big)) && (n_wide_big == 0 || g.H != nullptr);
 }
 
+constexpr int64_t SCATTER_GRID_CAP = GRID_MAX;  // blocks cap of the per-source scatter
+
 hipError_t launch_gossip_scatter(const DevGraph& g, const DevState& st, const RoundParams& p,
                                  const int64_t* hub_items, int64_t n_hub_items, bool store_e,
                                  hipStream_t s, const int64_t* big_items, int64_t n_big,
                                  const int32_t* wide_big, int64_t n_wide_big) {
-  // blocks cap: P2PG_SCATTER_GRID (default GRID_MAX)
-  static const int64_t cap = [] {
-    const char* e = std::getenv("P2PG_SCATTER_GRID");
-    const int64_t v = e ? std::atoll(e) : GRID_MAX;
-    return v > 0 ? v : (int64_t)GRID_MAX;
-  }();
   const int grid = (int)std::min<int64_t>(
-      grid_tasks_uncapped(((g.V + 31) >> 5) + ((n_hub_items + 63) >> 6)), cap);
-  static const bool push_grouped = [] {  // P2PG_PUSH_GROUPED=0: one wave per source (A/B)
-    const char* e = std::getenv("P2PG_PUSH_GROUPED");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
+      grid_tasks_uncapped(((g.V + 31) >> 5) + ((n_hub_items + 63) >> 6)), SCATTER_GRID_CAP);
   const bool hubs_ok = hub_pushes_ready(g, big_items, n_big, wide_big, n_wide_big);
-  if (store_e && push_grouped && grouped_enabled() && st.W <= GROUPED_W_MAX && hubs_ok && !g.gid) {
+  // narrow rows (W <= GROUPED_W_MAX: one rank's share of a message split): several peers per wave
+  if (store_e && st.W <= GROUPED_W_MAX && hubs_ok && !g.gid) {
     hipError_t r = launch_gossip_push_grouped(g, st, p, s);
     if (r != hipSuccess) return r;
     return launch_wide_push_e(g, st, p, big_items, n_big, wide_big, n_wide_big, s);
@@ -2842,19 +2616,9 @@ hipError_t launch_gossip_scatter(const DevGraph& g, const DevState& st, const Ro
   const char* pf_env = std::getenv("P2PG_PUSH_FUSED");
   const bool push_fused = !(pf_env && std::strcmp(pf_env, "0") == 0);
   if (store_e && push_fused && st.W <= 64 && st.AW[p.round & 1] != nullptr && hubs_ok && !g.gid) {
-#define P2PG_FUSED_PO(CH, KK)                                                                       \
-  hipLaunchKernelGGL((k_gossip_fused<CH, KK, 1>),                                                 \
-                     dim3(balanced_grid(k_gossip_fused<CH, KK, 1>, (g.V + 31) >> 5)), dim3(256),    \
-                     0, s, g, st, p)
-    const bool ch = p.churn_thr != 0;
-    switch (p.fanout) {
-      case 1: if (ch) P2PG_FUSED_PO(true, 1); else P2PG_FUSED_PO(false, 1); break;
-      case 2: if (ch) P2PG_FUSED_PO(true, 2); else P2PG_FUSED_PO(false, 2); break;
-      case 3: if (ch) P2PG_FUSED_PO(true, 3); else P2PG_FUSED_PO(false, 3); break;
-      case 4: if (ch) P2PG_FUSED_PO(true, 4); else P2PG_FUSED_PO(false, 4); break;
-      default: if (ch) P2PG_FUSED_PO(true, 0); else P2PG_FUSED_PO(false, 0); break;
-    }
-#undef P2PG_FUSED_PO
+    dispatch_fanout_churn(p, [&](auto ch, auto k) {
+      fused_launch<decltype(ch)::value, decltype(k)::value, 1>(g, st, p, s);
+    });
     hipError_t r = hipGetLastError();
     if (r != hipSuccess) return r;
     return launch_wide_push_e(g, st, p, big_items, n_big, wide_big, n_wide_big, s);
@@ -2866,20 +2630,9 @@ hipError_t launch_gossip_scatter(const DevGraph& g, const DevState& st, const Ro
   return hipGetLastError();
 }
 
-// narrow rows (W <= GROUPED_W_MAX: one rank's share of a message split): several peers per
-// wave.
-// P2PG_GROUPED=0 keeps one wave per peer (A/B only; needs packed rows).
-static bool grouped_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("P2PG_GROUPED");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  return on;
-}
-
 bool gossip_update_push_supported(const DevState& st) {
-  return st.W > 16 && st.W <= 64 && st.AW[0] != nullptr && st.E[0] != nullptr &&
-         !(grouped_enabled() && st.W <= GROUPED_W_MAX);
+  return st.W > 16 && st.W > GROUPED_W_MAX && st.W <= 64 && st.AW[0] != nullptr &&
+         st.E[0] != nullptr;
 }
 
 hipError_t launch_gossip_update_push(const DevGraph& g, const DevState& st, const RoundParams& p,
@@ -2888,19 +2641,9 @@ hipError_t launch_gossip_update_push(const DevGraph& g, const DevState& st, cons
   if (!gossip_update_push_supported(st) || p.phase >= 0 ||
       !hub_pushes_ready(g, big_items, n_big, wide_big, n_wide_big))
     return hipErrorInvalidValue;
-#define P2PG_FUSED_UP(CH, KK)                                                                       \
-  hipLaunchKernelGGL((k_gossip_fused<CH, KK, 2>),                                                 \
-                     dim3(balanced_grid(k_gossip_fused<CH, KK, 2>, (g.V + 31) >> 5)), dim3(256),    \
-                     0, s, g, st, p)
-  const bool ch = p.churn_thr != 0;
-  switch (p.fanout) {
-    case 1: if (ch) P2PG_FUSED_UP(true, 1); else P2PG_FUSED_UP(false, 1); break;
-    case 2: if (ch) P2PG_FUSED_UP(true, 2); else P2PG_FUSED_UP(false, 2); break;
-    case 3: if (ch) P2PG_FUSED_UP(true, 3); else P2PG_FUSED_UP(false, 3); break;
-    case 4: if (ch) P2PG_FUSED_UP(true, 4); else P2PG_FUSED_UP(false, 4); break;
-    default: if (ch) P2PG_FUSED_UP(true, 0); else P2PG_FUSED_UP(false, 0); break;
-  }
-#undef P2PG_FUSED_UP
+  dispatch_fanout_churn(p, [&](auto ch, auto k) {
+    fused_launch<decltype(ch)::value, decltype(k)::value, 2>(g, st, p, s);
+  });
   hipError_t r = hipGetLastError();
   if (r != hipSuccess) return r;
   if (g.H) {
@@ -2909,7 +2652,7 @@ hipError_t launch_gossip_update_push(const DevGraph& g, const DevState& st, cons
     RoundParams ph = p;
     ph.border = g.H;
     ph.phase = 1;
-    const int grid = (int)std::min<int64_t>(grid_tasks((g.V + 31) >> 5), 1024);
+    const int grid = (int)std::min<int64_t>(grid_tasks((g.V + 31) >> 5), UPDATE_GRID_CAP);
     hipLaunchKernelGGL(k_gossip_update1<1>, dim3(grid), dim3(256), 0, s, g, st, ph);
     r = hipGetLastError();
     if (r != hipSuccess) return r;
@@ -2919,7 +2662,7 @@ hipError_t launch_gossip_update_push(const DevGraph& g, const DevState& st, cons
 
 bool gossip_fused_supported(const DevState& st) {
   if (st.W > 64 || st.E[0] == st.E[1]) return false;
-  return (grouped_enabled() && st.W <= GROUPED_W_MAX) || st.AW[0] != nullptr;
+  return st.W <= GROUPED_W_MAX || st.AW[0] != nullptr;
 }
 
 hipError_t launch_gossip_fused(const DevGraph& g, const DevState& st, const RoundParams& p,
@@ -2929,36 +2672,13 @@ hipError_t launch_gossip_fused(const DevGraph& g, const DevState& st, const Roun
   if (g.gid) return launch_gossip_fused_part(g, st, p, s);  // (the caller clears the arrivals)
   if (hp.n_items)
     launch_hub_partial<false, true>(g, st, p, hp, s);
-  if (grouped_enabled() && st.W <= GROUPED_W_MAX) {
+  if (st.W <= GROUPED_W_MAX) {
     hipError_t r = launch_gossip_fused_grouped(g, st, p, s);
     if (r != hipSuccess) return r;
   } else {
-#define P2PG_FUSED(CH, KK)                                                                       \
-  do {                                                                                         \
-    if (half)                                                                                  \
-      hipLaunchKernelGGL((k_gossip_fused<CH, KK, 0, true>),                                    \
-                         dim3(balanced_grid(k_gossip_fused<CH, KK, 0, true>, (g.V + 31) >> 5)), \
-                         dim3(256), 0, s, g, st, p);                                           \
-    else                                                                                       \
-      hipLaunchKernelGGL((k_gossip_fused<CH, KK>),                                             \
-                         dim3(balanced_grid(k_gossip_fused<CH, KK>, (g.V + 31) >> 5)), dim3(256), \
-                         0, s, g, st, p);                                                      \
-  } while (0)
-  // W <= 32: two slots per gather load (P2PG_FUSED_HALF=0: one, A/B only)
-  static const bool half_on = [] {
-    const char* e = std::getenv("P2PG_FUSED_HALF");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  const bool half = half_on && st.W <= 32;
-  const bool ch = p.churn_thr != 0;
-  switch (p.fanout) {
-    case 1: if (ch) P2PG_FUSED(true, 1); else P2PG_FUSED(false, 1); break;
-    case 2: if (ch) P2PG_FUSED(true, 2); else P2PG_FUSED(false, 2); break;
-    case 3: if (ch) P2PG_FUSED(true, 3); else P2PG_FUSED(false, 3); break;
-    case 4: if (ch) P2PG_FUSED(true, 4); else P2PG_FUSED(false, 4); break;
-    default: if (ch) P2PG_FUSED(true, 0); else P2PG_FUSED(false, 0); break;
-  }
-#undef P2PG_FUSED
+    dispatch_fanout_churn(p, [&](auto ch, auto k) {
+      fused_launch_w<decltype(ch)::value, decltype(k)::value, 0>(g, st, p, s);
+    });
   }
   if (hp.n_hubs)
     hipLaunchKernelGGL((k_pull_hub_finalize<true>), dim3(grid_tasks(hp.n_hubs)), dim3(256), 0,

@@ -52,14 +52,8 @@ __device__ __forceinline__ int pass_owner(uint32_t* own, int lane, uint32_t pos,
 // list counter took one same-address atomic per 64 peers: ~8 ns each, serialized (0.1-1.2 ms
 // per round).  Chunks are small because the Barabasi-Albert hubs (lowest ids, most active
 // words) share the first tasks.
-#ifndef P2PG_SW_TASKS
-#define P2PG_SW_TASKS 16
-#endif
-constexpr int SW_TASKS = P2PG_SW_TASKS;
-#ifndef P2PG_SPARSE_GRID_MAX
-#define P2PG_SPARSE_GRID_MAX 8192
-#endif
-constexpr int64_t SPARSE_GRID_MAX = P2PG_SPARSE_GRID_MAX;
+constexpr int SW_TASKS = 16;
+constexpr int64_t SPARSE_GRID_MAX = 8192;  // blocks of a sparse-round launch (see its launcher)
 
 template <bool WRITE>
 __global__ __launch_bounds__(256) void k_sparse_words(DevGraph g, DevState st, RoundParams p,
@@ -457,17 +451,10 @@ hipError_t launch_gossip_scatter_sparse(const DevGraph& g, const DevState& st,
   hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, s, chunks, b);
   hipLaunchKernelGGL(k_sparse_words<true>, dim3(wgrid), dim3(256), 0, s, g, st, p, b);
   const int grid = sgrid((expect + 63) >> 6);  // 64 listed words per wave pass
-  const bool ch = p.churn_thr != 0;
-#define P2PG_SPARSE(CH, KK) \
-  hipLaunchKernelGGL((k_sparse_push<CH, KK>), dim3(grid), dim3(256), 0, s, g, st, p, b)
-  switch (p.fanout) {
-    case 1: if (ch) P2PG_SPARSE(true, 1); else P2PG_SPARSE(false, 1); break;
-    case 2: if (ch) P2PG_SPARSE(true, 2); else P2PG_SPARSE(false, 2); break;
-    case 3: if (ch) P2PG_SPARSE(true, 3); else P2PG_SPARSE(false, 3); break;
-    case 4: if (ch) P2PG_SPARSE(true, 4); else P2PG_SPARSE(false, 4); break;
-    default: if (ch) P2PG_SPARSE(true, 0); else P2PG_SPARSE(false, 0); break;
-  }
-#undef P2PG_SPARSE
+  dispatch_fanout_churn(p, [&](auto ch, auto k) {
+    hipLaunchKernelGGL((k_sparse_push<decltype(ch)::value, decltype(k)::value>), dim3(grid), dim3(256), 0, s,
+                       g, st, p, b);
+  });
   const int64_t ntasks = (g.V + 31) >> 5;
   hipLaunchKernelGGL(k_touched_bits, dim3((unsigned)std::min<int64_t>((ntasks + 255) / 256, 4096)),
                      dim3(256), 0, s, g.V, st.T[(p.round & 1) ^ 1], b.touched);
@@ -482,17 +469,10 @@ hipError_t launch_wide_push_e(const DevGraph& g, const DevState& st, const Round
   hipLaunchKernelGGL(k_wide_zero, dim3(grid_tasks((n_items + 3) >> 2)), dim3(256), 0, s, g, st,
                      p, items, n_items);
   const int grid = grid_tasks(n_wide);
-  const bool ch = p.churn_thr != 0;
-#define P2PG_WIDE(CH, KK) \
-  hipLaunchKernelGGL((k_wide_push<CH, KK>), dim3(grid), dim3(256), 0, s, g, st, p, wide, n_wide)
-  switch (p.fanout) {
-    case 1: if (ch) P2PG_WIDE(true, 1); else P2PG_WIDE(false, 1); break;
-    case 2: if (ch) P2PG_WIDE(true, 2); else P2PG_WIDE(false, 2); break;
-    case 3: if (ch) P2PG_WIDE(true, 3); else P2PG_WIDE(false, 3); break;
-    case 4: if (ch) P2PG_WIDE(true, 4); else P2PG_WIDE(false, 4); break;
-    default: if (ch) P2PG_WIDE(true, 0); else P2PG_WIDE(false, 0); break;
-  }
-#undef P2PG_WIDE
+  dispatch_fanout_churn(p, [&](auto ch, auto k) {
+    hipLaunchKernelGGL((k_wide_push<decltype(ch)::value, decltype(k)::value>), dim3(grid), dim3(256), 0, s, g,
+                       st, p, wide, n_wide);
+  });
   return hipGetLastError();
 }
 
