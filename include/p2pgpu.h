@@ -15,6 +15,8 @@
  *   p2pg_set_sources_at /         <- the same call made later in the run: an app says something
  *   p2pg_originate                   whenever it has something to say (node.py:106-112), so each
  *                                    broadcast has its own start round
+ *   p2pg_set_ttl                  <- a hop budget in the payload, forwarded as ttl - 1 while
+ *                                    ttl > 0 (README.md:20; the sends are node.py:106-116)
  *   p2pg_step / p2pg_run          <- one / all rounds of: NodeConnection.run receive loop
  *                                    (nodeconnection.py:186-218) -> Node.node_message
  *                                    (node.py:334-338) -> app dedup -> send_to_nodes(data,
@@ -181,6 +183,36 @@ int p2pg_set_sources_at(p2pg_engine* e, int32_t M, const int32_t* src, const int
  * nothing changed).  Wakes an engine that had gone quiet.  P2PG_ERR_STATE between
  * p2pg_step_begin / p2pg_step_end and on a vertex-partitioned rank.                        */
 int p2pg_originate(p2pg_engine* e, int64_t n, const int32_t* msg, const int32_t* peer, int32_t round);
+/* Hop limits: the hop budget an app puts into its payload and forwards as ttl - 1 while
+ * ttl > 0 (README.md:20: the app decides whether its node_message calls send_to_nodes,
+ * node.py:106-116).  ttl[m] >= 0 bounds message m, -1 leaves it unlimited.  A first receipt of m
+ * in round r has relative hop h = r - start[m] (the origination is the receipt with h = 0).  It
+ * happens exactly as without a limit -- seen bit, hop r, parent, new_deliveries and the other
+ * receipt counters, the delivery stream, reach / hop_sum / last_hop -- and makes its sends iff
+ * ttl[m] < 0 or h < ttl[m].  A receipt with h == ttl[m] makes none: they are in no round's
+ * `relays`, no next round's `received` (with or without P2PG_FLAG_RECEIVED), not in
+ * p2pg_get_sends, p2pg_peer_counters or the lost-send count; ttl 0 = the origin marks the message
+ * seen and sends nothing.  So m has nothing in flight after its expiry round start[m] + ttl[m],
+ * and a run with hop limits is the unlimited run cut off at relative hop ttl[m], message by
+ * message, under churn and in gossip as well.  Hops stay absolute; `active` keeps its rule.
+ * Call it after p2pg_set_sources / p2pg_set_sources_at and before round 0 runs, or after a
+ * p2pg_reset: M = the engine's message count, every ttl[m] in [-1, 2^30] (P2PG_ERR_ARG
+ * otherwise).  An unscheduled message keeps its limit for the round p2pg_originate gives it.
+ * All -1, or ttl = NULL, removes the limits: the engine is then exactly the engine without this
+ * call.  p2pg_reset keeps them and replays them; p2pg_set_sources[_at] clears them.
+ * P2PG_ERR_STATE on a vertex-partitioned rank, between p2pg_step_begin / p2pg_step_end and once a
+ * round has run; while a finite limit is set p2pg_snapshot / p2pg_restore return P2PG_ERR_STATE.
+ * A rejected call changes nothing.
+ * An expiry round's sends become final at the start of the next round or inside p2pg_get_sends,
+ * p2pg_peer_counters, p2pg_update_edges or p2pg_drop_relays, whichever comes first: read the
+ * round's deliveries before those (as for p2pg_drop_relays) -- they hold all its receipts, the
+ * expired messages' last ones included; afterwards p2pg_get_new_deliveries for that round returns
+ * P2PG_ERR_STATE, never a shortened list.  p2pg_drop_relays of an expired receipt is legal and
+ * cancels nothing.  A gossip expiry round runs the unfused schedule and its pushes leave by row
+ * atomics when its sends become final: its scatter_words is 0 and its push_form
+ * P2PG_PUSH_ATOMIC, and the next round's touched_words counts what that push touched (DESIGN.md
+ * 4j).  Rounds without an expiry keep every form they have.                                    */
+int p2pg_set_ttl(p2pg_engine* e, int32_t M, const int32_t* ttl);
 /* Back to round 0 with the same graph, sources and start rounds (clears seen/frontier state). */
 int p2pg_reset(p2pg_engine* e);
 /* One round. Returns 1 while messages are in flight, 0 when quiescent, < 0 on error. */
@@ -255,7 +287,7 @@ int p2pg_message_tally(p2pg_engine* e, uint64_t* reach, uint64_t* hop_sum, int32
  * a boundary.  p2pg_reset and p2pg_set_sources zero all tallies. */
 int p2pg_peer_counters(p2pg_engine* e, uint64_t* sent, uint64_t* received);
 /* Summed device time per kernel class since the last reset (needs P2PG_FLAG_TIMING):
- * 0 seed (origination, in round 0 and later), 1 flood pull, 2 gossip scatter by row atomics (sparse rounds),
+ * 0 seed (origination, in round 0 and later; the hop-limit passes of expiry rounds), 1 flood pull, 2 gossip scatter by row atomics (sparse rounds),
  * 3 record (validation), 4 gossip update (consume row atomics), 5 gossip pull (consume edge
  * stores), 6 gossip scatter by edge stores (dense rounds), 7 gossip fused pull + scatter
  * (a dense round after a dense round).                                                  */

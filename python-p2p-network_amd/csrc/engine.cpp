@@ -17,6 +17,11 @@
 //                  is r, after the receive pass (relay_originate.hip); such a gossip round is
 //                  never fused: update / pull, originate, then the separate scatter
 //   record         hop/parent planes for the bits of F[r&1]   (P2PG_FLAG_RECORD only)
+//   expire         a round in which hop limits run out (p2pg_set_ttl; relay_expire.hip) runs the
+//                  unfused schedule too; after record and the tally count the relays of its
+//                  expired first receipts leave its counters, and when its sends become final (the
+//                  next round's start or a boundary call) their frontier bits are cleared -- then,
+//                  gossip, its held-back push leaves by row atomics
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -220,6 +225,18 @@ struct p2pg_engine {
   int32_t* d_sched_peer = nullptr;
   int32_t* d_sched_msg = nullptr;
   int64_t* d_sched_grp = nullptr;
+  // Hop limits (p2pg_set_ttl): h_ttl[m] >= 0, or -1 = unlimited (empty: none set).  A scheduled
+  // message expires in round start[m] + ttl[m]; exp_rounds holds those rounds, ascending, and d_exp
+  // two W-word masks per round i (relay_expire.hip): X at (2 i) W, Z at (2 i + 1) W.  Uploaded
+  // when the limits or the schedule change, not per round.
+  std::vector<int32_t> h_ttl;
+  bool ttl_on = false;           // some hop limit is finite
+  std::vector<int32_t> exp_rounds;
+  uint64_t* d_exp = nullptr;
+  int32_t exp_pending = -1;      // the expiry round whose sends are not final yet: its expired
+                                 // frontier bits still stand (they serve its delivery stream) and
+                                 // its gossip push is held back (finalize_expiry)
+  int32_t exp_final = -1;        // the last expiry round whose frontier bits were cleared
 };
 
 namespace {
@@ -300,6 +317,11 @@ void free_state(p2pg_engine* e) {
   e->sched_rounds.clear();
   e->late = false;
   e->last_start = 0;
+  dfree(e->d_exp);
+  e->exp_rounds.clear();
+  e->h_ttl.clear();
+  e->ttl_on = false;
+  e->exp_pending = e->exp_final = -1;
   e->have_state = false;
 }
 
@@ -1030,6 +1052,108 @@ bool start_ahead(const p2pg_engine* e, int32_t r) { return e->last_start >= r &&
 // Is this engine a rank of a vertex partition?
 bool partitioned(const p2pg_engine* e) { return e->d_gid || (e->cfg.flags & P2PG_FLAG_LOCAL_GRAPH); }
 
+// The device expiry schedule from h_ttl / h_start: the rounds in which a scheduled message with a
+// finite hop limit expires and their X / Z masks.  Runs when the limits or the schedule change
+// (set_ttl, originate); an unscheduled message has no expiry round until p2pg_originate gives it
+// a start.
+int upload_expiry(p2pg_engine* e) {
+  const int32_t M = e->M, W = e->W;
+  std::vector<std::pair<int64_t, int32_t>> xs;  // (expiry round, message)
+  e->ttl_on = false;
+  for (int32_t m = 0; m < M && !e->h_ttl.empty(); ++m) {
+    if (e->h_ttl[m] < 0) continue;
+    e->ttl_on = true;
+    const int64_t x = (int64_t)e->h_start[m] + e->h_ttl[m];
+    if (e->h_start[m] >= 0 && x <= 0x7FFFFFFFll) xs.emplace_back(x, m);
+  }
+  std::sort(xs.begin(), xs.end());
+  e->exp_rounds.clear();
+  std::vector<uint64_t> masks;
+  for (const auto& xm : xs) {
+    if (e->exp_rounds.empty() || e->exp_rounds.back() != (int32_t)xm.first) {
+      e->exp_rounds.push_back((int32_t)xm.first);
+      masks.resize(masks.size() + 2 * (size_t)W, 0ull);
+    }
+    uint64_t* const X = masks.data() + masks.size() - 2 * (size_t)W;
+    const int32_t m = xm.second;
+    X[m >> 6] |= 1ull << (m & 63);
+    if (e->h_ttl[m] == 0) X[W + (m >> 6)] |= 1ull << (m & 63);
+  }
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  // (the stream may still run a pass that reads the old masks)
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  dfree(e->d_exp);
+  if (!masks.empty()) {
+    HIPCHK(e, hipMalloc((void**)&e->d_exp, sizeof(uint64_t) * masks.size()));
+    HIPCHK(e, hipMemcpy(e->d_exp, masks.data(), sizeof(uint64_t) * masks.size(), hipMemcpyHostToDevice));
+  }
+  e->seed.ok = false;  // (round 0's relays leave out the ttl-0 originations)
+  return P2PG_OK;
+}
+
+// Index into exp_rounds of round r's expiries, or -1.
+int64_t expiry_index(const p2pg_engine* e, int32_t r) {
+  if (e->exp_rounds.empty() || r > e->exp_rounds.back()) return -1;
+  auto it = std::lower_bound(e->exp_rounds.begin(), e->exp_rounds.end(), r);
+  return it != e->exp_rounds.end() && *it == r ? (int64_t)(it - e->exp_rounds.begin()) : -1;
+}
+
+// Does an expiry lie at or after round r?
+bool expiry_ahead(const p2pg_engine* e, int32_t r) {
+  return !e->exp_rounds.empty() && e->exp_rounds.back() >= r;
+}
+
+// Does message m expire in round r?
+bool expires_in(const p2pg_engine* e, int32_t m, int32_t r) {
+  return !e->h_ttl.empty() && e->h_ttl[m] >= 0 && e->h_start[m] >= 0 &&
+         (int64_t)e->h_start[m] + e->h_ttl[m] == (int64_t)r;
+}
+
+// The sends of the pending expiry round become final: its expired frontier bits are cleared
+// (from here on p2pg_get_new_deliveries refuses that round), then -- push -- a gossip round's
+// held-back pushes leave as row atomics into the planes the next round's update consumes (no
+// push is made twice, no plane zeroed), and a churn run with P2PG_FLAG_RECEIVED counts the
+// round's lost sends, which it could not before the clearing.  Called at the top of the next
+// round, before the peer counters take the round in, and by the boundary calls that read or
+// change the round's sends; drop_relays and update_edges redo the gossip pushes themselves
+// (push = false).
+// Returns a P2PG code.  The passes are timed with their classes: k_expire with the origination
+// class 0 (like k_originate, a pass over the schedule's messages), the push with class 2.
+int finalize_expiry(p2pg_engine* e, bool push) {
+  if (e->exp_pending < 0) return P2PG_OK;
+  const int32_t r = e->exp_pending;
+  const int64_t xi = expiry_index(e, r);
+  if (xi < 0) {
+    e->exp_pending = -1;
+    return P2PG_OK;
+  }
+  RoundParams p = params(e);
+  p.round = r;
+  const DevGraph g = graph(e);
+  const uint64_t* X = e->d_exp + 2 * (size_t)xi * e->W;
+  int rc = timed(e, 0, [&] { return launch_expire(g, e->st, p, X, X + e->W, true, e->stream); });
+  if (rc) return rc;
+  // the bits are gone (stream order): the round is final whatever happens below
+  e->exp_pending = -1;
+  e->exp_final = r;
+  if (push && e->cfg.mode == P2PG_MODE_GOSSIP && e->last_new > 0) {
+    // The list is sized by the round's nonzero frontier words before the clearing (prev_aw), which
+    // bounds the words left after it: this push cannot outgrow its list, so its count is not read
+    // back (check_scatter_list would cost the boundary a host synchronisation).
+    rc = timed(e, 2, [&] { return launch_scatter_atomic(e, g, p, std::max<uint64_t>(e->prev_aw, 1)); });
+    e->wlist_check = false;
+    e->stats_clear = true;  // the push counted into the round counters
+    if (rc) return rc;
+  }
+  if (count_lost_on(e)) {
+    hipError_t x = enqueue_lost_count(e, g, graph_for_arrivals(e, r), r);
+    if (x == hipSuccess) x = hipStreamSynchronize(e->stream);
+    if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("hop limits (lost sends): ") + hipGetErrorString(x));
+    e->lost_last = (uint64_t)e->h_cnt2[1];
+  }
+  return P2PG_OK;
+}
+
 // p2pg_set_sources (start == nullptr: every message starts in round 0) / p2pg_set_sources_at
 int set_sources(p2pg_engine* e, const char* what, int32_t M, const int32_t* src, const int32_t* start) {
   const std::string w(what);
@@ -1063,6 +1187,10 @@ int set_sources(p2pg_engine* e, const char* what, int32_t M, const int32_t* src,
   }
   int rc = upload_schedule(e);
   if (rc) return rc;
+  if (!e->h_ttl.empty()) {  // new sources carry no hop limits
+    e->h_ttl.clear();
+    if ((rc = upload_expiry(e))) return rc;
+  }
   return p2pg_reset(e);
 }
 
@@ -1106,8 +1234,32 @@ int p2pg_originate(p2pg_engine* e, int64_t n, const int32_t* msg, const int32_t*
   }
   int rc = upload_schedule(e);
   if (rc) return rc;
+  if (e->ttl_on && (rc = upload_expiry(e))) return rc;  // (the new starts fix their expiry rounds)
   e->done = false;  // (an engine that had gone quiet runs on: a start lies ahead)
   return P2PG_OK;
+}
+
+int p2pg_set_ttl(p2pg_engine* e, int32_t M, const int32_t* ttl) {
+  if (!e) return fail(e, P2PG_ERR_ARG, "set_ttl: no engine");
+  if (!e->have_state) return fail(e, P2PG_ERR_STATE, "set_ttl: no sources set");
+  if (M != e->M) return fail(e, P2PG_ERR_ARG, "set_ttl: M differs from the engine's message count");
+  bool finite = false;
+  for (int32_t m = 0; ttl && m < M; ++m) {
+    if (ttl[m] < -1 || ttl[m] > (1 << 30))
+      return fail(e, P2PG_ERR_ARG, "set_ttl: a hop limit must lie in [-1, 2^30]");
+    finite |= ttl[m] >= 0;
+  }
+  if (partitioned(e))
+    return fail(e, P2PG_ERR_STATE, "set_ttl: hop limits are not available on a vertex-partitioned rank");
+  if (e->begun) return fail(e, P2PG_ERR_STATE, "set_ttl: a round has begun (step_begin)");
+  if (e->round > 0) return fail(e, P2PG_ERR_STATE, "set_ttl: a round has run (set the hop limits before round 0, or after p2pg_reset)");
+  if (!e->failed.empty()) return fail(e, P2PG_ERR_STATE, "set_ttl: " + e->failed);
+  if (!finite && e->h_ttl.empty()) return P2PG_OK;  // nothing set, nothing to remove
+  if (finite)
+    e->h_ttl.assign(ttl, ttl + M);
+  else
+    e->h_ttl.clear();  // all -1 (or NULL): the engine without this call
+  return upload_expiry(e);
 }
 
 }  // extern "C"
@@ -1130,7 +1282,8 @@ const SeedStats& seed_stats(p2pg_engine* e) {
     if (e->h_start[m] != 0) continue;
     const int64_t v = e->h_src[m];
     const int64_t d = e->h_rowptr[v + 1] - e->h_rowptr[v];
-    ss.relays += gossip ? (uint64_t)std::min<int64_t>(d, e->cfg.fanout) : (uint64_t)d;
+    if (!expires_in(e, m, 0))  // (ttl 0: the origin marks the message seen and sends nothing)
+      ss.relays += gossip ? (uint64_t)std::min<int64_t>(d, e->cfg.fanout) : (uint64_t)d;
     vs.push_back(v);
     vw.push_back(v * e->W + (m >> 6));
   }
@@ -1230,6 +1383,7 @@ int p2pg_reset(p2pg_engine* e) {
   }
   e->tally_pending = -1;
   e->tally_read_at = -1;
+  e->exp_pending = e->exp_final = -1;  // (the hop limits themselves stay and are replayed)
   e->round = 0;
   e->done = false;
   e->failed.clear();
@@ -1283,6 +1437,10 @@ int p2pg_step_begin(p2pg_engine* e) {
   if (e->done) return P2PG_OK;
   HIPCHK(e, hipSetDevice(e->cfg.device));
   DevState& s = e->st;
+  {  // hop limits: the last round's expired receipts send nothing (before anything reads its sends)
+    const int xrc = finalize_expiry(e, true);
+    if (xrc) return xrc;
+  }
   {  // tallies: the last round's sends are final; its frontiers are overwritten from here on
     const hipError_t x = flush_peer_tally(e, graph(e));
     if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("step (peer counters): ") + hipGetErrorString(x));
@@ -1338,8 +1496,13 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   // cannot be ORed into) and its own counters read before the push (the last round's pushed masks
   // do not bound words nobody pushed).  The rounds around it keep every form they have.
   const p2pg_engine::SchedRound* const orig = sched_round(e, e->round);
+  // A round in which hop limits expire (p2pg_set_ttl) is treated alike: the unfused schedule with
+  // whole frontier rows, which the correction pass and the boundary's clearing read and write
+  // (relay_expire.hip); its gossip push is held back until its sends are final (finalize_expiry).
+  const int64_t xi = expiry_index(e, e->round);
+  const bool plain = orig != nullptr || xi >= 0;
   // the update / pull-only pass of this round (fused and update+push rounds set their own)
-  if (gossip && !orig && partial_frontier(e, e->skip_frontier)) p.store_f = 2;
+  if (gossip && !plain && partial_frontier(e, e->skip_frontier)) p.store_f = 2;
   uint64_t host_new = 0, host_relays = 0, host_av = 0, host_aw = 0, host_wedge = 0, host_degact = 0;
   if (e->round == 0) {
     if ((rc = timed(e, 0, [&] { return launch_zero_rows(s.F[0], e->W, e->d_src, e->M, e->stream); }))) return rc;
@@ -1366,7 +1529,7 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     // the push form, never the result), the same pass also pushes this round's receipts.
     const bool dense_pred = e->push_mode == 2 || (e->push_mode == 0 && still_dense(e));
     const bool part = e->d_gid != nullptr;  // (a rank gets here only if part_dense)
-    fused_round = !orig && (!part || part_dense(e)) && dense_pred && gossip_fused_supported(s);
+    fused_round = !plain && (!part || part_dense(e)) && dense_pred && gossip_fused_supported(s);
     if (fused_round) {
       // a frontier nobody observes is not stored: inside p2pg_run (not its last allowed
       // round), without hop/parent records
@@ -1379,7 +1542,7 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
            })))
         return rc;
     }
-  } else if (!orig && update_push_round(e, p)) {
+  } else if (!plain && update_push_round(e, p)) {
     // the first dense round after a sparse one: update and E pushes in one pass (timed with the
     // store pushes); the frontier rows follow the fused rounds' rule
     up_round = true;
@@ -1425,6 +1588,10 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   };
   if (gossip && (fused_round || up_round)) {
     e->last_push_e = true;  // the fused launches pushed every source of this round
+  } else if (gossip && xi >= 0) {
+    // an expiry round: its pushes wait until the expired frontier bits are cleared, when its sends
+    // become final (finalize_expiry: row atomics into the planes the next round's update consumes)
+    e->last_push_e = false;
   } else if (gossip) {
     // push form for this round's sends: row atomics when the frontier is sparse, whole-row
     // edge-mask stores (+ pull next round) when most words of the active rows are set
@@ -1433,7 +1600,7 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     // that choice is clear already) and to size the sparse push's (peer, word) list (else
     // bounded by the last round's pushed masks).  Not on a vertex-partitioned rank: rows other
     // ranks pushed arrive by the exchange, so this rank's own pushed masks bound nothing
-    const bool blind = e->round > 0 && e->push_mode != 2 && !e->d_gid && !orig && clearly_sparse(e) &&
+    const bool blind = e->round > 0 && e->push_mode != 2 && !e->d_gid && !plain && clearly_sparse(e) &&
                        e->prev_sw > 0;
     // (partitioned ranks: E for their local connections when part_dense, ghost rows travel)
     if (s.E[0] && (!e->d_gid || part_dense(e))) {
@@ -1505,7 +1672,18 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("step (message tallies): ") + hipGetErrorString(x));
     e->tally_pending = e->round;
   }
-  const bool cnt_lost = count_lost_on(e);
+  if (xi >= 0) {
+    // hop limits: the receive pass and k_originate counted every first receipt's relays; the
+    // expired ones leave this round's total (round 0's are the host's: seed_stats).  Their frontier
+    // bits stand until the round's sends are final -- they are the round's deliveries
+    if (e->round > 0) {
+      const uint64_t* X = e->d_exp + 2 * (size_t)xi * e->W;
+      if ((rc = timed(e, 0, [&] { return launch_expire(g, s, p, X, X + e->W, false, e->stream); }))) return rc;
+    }
+    e->exp_pending = e->round;
+  }
+  // (an expiry round's lost sends are counted once its expired bits are cleared: finalize_expiry)
+  const bool cnt_lost = count_lost_on(e) && xi < 0;
   if (cnt_lost) {  // this round's lost sends: the next round's arrivals are its sends minus them
     hipError_t x = enqueue_lost_count(e, g, graph_for_arrivals(e, e->round), e->round);
     if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("step (lost sends): ") + hipGetErrorString(x));
@@ -1590,6 +1768,8 @@ static bool decay_batchable(const p2pg_engine* e) {
          // under the older ones' decay and outgrow it mid-batch, and an origination round reads its
          // own counters before its push
          e->last_start == 0 &&
+         // no hop limit expires from here on: an expiry round runs its own schedule (p2pg_step)
+         !expiry_ahead(e, e->round) &&
          !e->d_gid && !(e->cfg.flags & P2PG_FLAG_NO_AUTOSTOP) && e->push_mode != 2 &&
          e->auto_buf == nullptr && sparse_scatter_on(e) &&
          e->last_new * 16 < (uint64_t)e->V;  // the tail: small rounds, where the syncs dominate
@@ -1736,6 +1916,10 @@ int p2pg_get_new_deliveries(p2pg_engine* e, int64_t cap, int32_t* peer, int32_t*
   }
   if (!e->frontier_kept)
     return fail(e, P2PG_ERR_STATE, "get_new_deliveries: the last round's frontier was not kept");
+  if (e->exp_final == e->round - 1)
+    return fail(e, P2PG_ERR_STATE, "get_new_deliveries: hop limits expired in the last round and its sends were "
+                                   "made final (get_sends, peer_counters, update_edges, drop_relays or "
+                                   "step_begin): read the round's deliveries first");
   if (!e->frontier_kept_prev)
     return fail(e, P2PG_ERR_STATE, "get_new_deliveries: the parents need the frontier of the round "
                                    "before, which was not kept (a fused round inside p2pg_run, or "
@@ -1815,6 +1999,10 @@ int p2pg_get_sends(p2pg_engine* e, int64_t cap, int32_t* sender, int32_t* receiv
     return P2PG_OK;
   }
   HIPCHK(e, hipSetDevice(e->cfg.device));
+  {  // hop limits: the expired receipts' sends do not exist
+    const int xrc = finalize_expiry(e, true);
+    if (xrc) return xrc;
+  }
   const int32_t r = e->round - 1;
   RoundParams p = params(e);
   p.round = r;
@@ -1889,8 +2077,16 @@ int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32
     return fail(e, P2PG_ERR_ARG, "drop_relays: a first receipt is listed twice");
   HIPCHK(e, hipSetDevice(e->cfg.device));
   const int32_t r = e->round - 1;
+  // Hop limits: a receipt of a message that expired in this round relays nothing, so dropping it
+  // is legal and cancels nothing.  Once the round's sends are final its frontier bits are gone and
+  // such an entry can no longer be checked against them: it is then taken as listed.
+  if (e->exp_final == r)
+    list.erase(std::remove_if(list.begin(), list.end(),
+                              [&](uint64_t x) { return expires_in(e, (int32_t)(uint32_t)x, r); }),
+               list.end());
+  n = (int64_t)list.size();
   uint64_t* dl = nullptr;
-  HIPCHK(e, hipMalloc((void**)&dl, sizeof(uint64_t) * n));
+  HIPCHK(e, hipMalloc((void**)&dl, sizeof(uint64_t) * (n ? n : 1)));
   hipError_t lr = hipMemcpyAsync(dl, list.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, e->stream);
   if (lr == hipSuccess) lr = hipMemsetAsync(e->d_cnt2, 0, 2 * sizeof(unsigned long long), e->stream);
   if (lr == hipSuccess) lr = launch_drop(e->st, r, dl, n, true, e->d_cnt2, e->stream);
@@ -1902,6 +2098,14 @@ int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32
     return fail(e, P2PG_ERR_ARG, "drop_relays: " + std::to_string(n - (int64_t)e->h_cnt2[0]) +
                                      " listed (peer, msg) are not first receipts of the last round");
   }
+  // (the listed receipts stand: now the round's expired bits go, then the listed ones)
+  if (lr == hipSuccess) {
+    const int xrc = finalize_expiry(e, false);
+    if (xrc) {
+      (void)hipFree(dl);
+      return xrc;
+    }
+  }
   if (lr == hipSuccess) lr = launch_drop(e->st, r, dl, n, false, nullptr, e->stream);
   if (lr == hipSuccess) lr = launch_rebuild_aw(e->st, r, e->V, e->stream);
   // the relays these receipts would have made (node.py:106-116): flood every connection but
@@ -1911,6 +2115,7 @@ int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32
     const int64_t v = (int64_t)(list[i] >> 32);
     const uint64_t deg = (uint64_t)(e->h_rowptr[v + 1] - e->h_rowptr[v]);
     const bool origin = e->h_start[(uint32_t)list[i]] == r;  // the message's own origination
+    if (expires_in(e, (int32_t)(uint32_t)list[i], r)) continue;  // (it made no relays to cancel)
     cancelled += gossip ? std::min<uint64_t>(deg, (uint64_t)e->cfg.fanout) : (origin ? deg : (deg ? deg - 1 : 0));
   }
   if (lr == hipSuccess && gossip) {
@@ -2033,6 +2238,10 @@ int p2pg_peer_counters(p2pg_engine* e, uint64_t* sent, uint64_t* received) {
   if (rc) return rc;
   HIPCHK(e, hipSetDevice(e->cfg.device));
   if (e->tally_pending >= 0) {
+    {  // hop limits: the expired receipts' sends do not exist
+      const int xrc = finalize_expiry(e, true);
+      if (xrc) return xrc;
+    }
     // the last round's sends count as they stand: a later drop or topology update at this
     // boundary would change sends already counted, so those calls refuse from here on
     const hipError_t x = flush_peer_tally(e, graph(e));
@@ -2053,6 +2262,9 @@ int p2pg_set_global_ids(p2pg_engine* e, const int32_t* gid) {
                                    "rank (ghost rows would be counted on two ranks)");
   if (gid && e->have_state && e->late)
     return fail(e, P2PG_ERR_STATE, "set_global_ids: start rounds other than 0 are not available on a "
+                                   "vertex-partitioned rank");
+  if (gid && e->have_state && e->ttl_on)
+    return fail(e, P2PG_ERR_STATE, "set_global_ids: hop limits (p2pg_set_ttl) are not available on a "
                                    "vertex-partitioned rank");
   HIPCHK(e, hipSetDevice(e->cfg.device));
   dfree(e->d_gid);
@@ -2336,6 +2548,11 @@ int p2pg_update_edges(p2pg_engine* e, int64_t n_add, const int32_t* add, int64_t
     // next[round&1] over the old graph minus the removed slots, before the graph changes.
     DevState& s = e->st;
     const bool gossip = e->cfg.mode == P2PG_MODE_GOSSIP;
+    {  // hop limits: the last round's expired receipts have nothing in flight (the gossip pushes
+       // are redone below)
+      const int xrc = finalize_expiry(e, false);
+      if (xrc) return xrc;
+    }
     std::vector<uint8_t> gone(ci.size(), 0);
     for (const auto& d : dels) gone[slot_of(d.first, d.second)] = 1;
     uint8_t* d_gone = nullptr;
@@ -2511,6 +2728,8 @@ int p2pg_snapshot(p2pg_engine* e, void* buf, int64_t cap) {
   if (e->late)
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold start rounds other than 0 "
                                    "(p2pg_set_sources_at / p2pg_originate)");
+  if (e->ttl_on)
+    return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold hop limits (p2pg_set_ttl)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "snapshot: a round has begun (step_begin)");
   if (e->arr_round >= 0 && e->arr_round == e->round)
     return fail(e, P2PG_ERR_STATE, "snapshot: take it before a topology update or after the next round");
@@ -2577,6 +2796,8 @@ int p2pg_restore(p2pg_engine* e, const void* buf, int64_t size) {
   if (e->late)
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold start rounds other than 0 "
                                    "(p2pg_set_sources_at / p2pg_originate)");
+  if (e->ttl_on)
+    return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold hop limits (p2pg_set_ttl)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "restore: a round has begun (step_begin)");
   SnapHeader h;
   std::memcpy(&h, buf, sizeof(h));

@@ -89,6 +89,7 @@ SIGNATURES = {
     "p2pg_set_sources": (ctypes.c_int, [_P, _I32, _P]),
     "p2pg_set_sources_at": (ctypes.c_int, [_P, _I32, _P, _P]),
     "p2pg_originate": (ctypes.c_int, [_P, _I64, _P, _P, _I32]),
+    "p2pg_set_ttl": (ctypes.c_int, [_P, _I32, _P]),
     "p2pg_reset": (ctypes.c_int, [_P]),
     "p2pg_step": (ctypes.c_int, [_P, ctypes.POINTER(RoundStatsC)]),
     "p2pg_run": (ctypes.c_int, [_P, _I32, _P, ctypes.POINTER(_I32)]),

@@ -161,6 +161,7 @@ class GraphNetwork:
         self._check(L.p2pg_load_csr(h, graph.V, _lib.ptr(graph.rowptr), _lib.ptr(graph.colidx)))
         self.sources = None
         self.start_rounds = None     # int32 [M]: the round each broadcast originates in (-1 = unscheduled)
+        self.ttl = None              # int32 [M]: each broadcast's hop limit (-1 = unlimited)
         self._autostop = bool(autostop)
         self._next_round = 0         # the next round the engine runs
         self._quiet = False          # the engine went quiet (further steps run no round)
@@ -202,9 +203,11 @@ class GraphNetwork:
         self._check(_lib.lib().p2pg_set_stream(self._h, ctypes.c_void_p(hip_stream or None)))
 
     # -- broadcasts -----------------------------------------------------------------------
-    def broadcast(self, sources, start_rounds=None):
+    def broadcast(self, sources, start_rounds=None, ttl=None):
         """Originate one broadcast per entry (origin peer ids); message m = position m.
         Equivalent of calling Node.send_to_nodes(data) at each origin (node.py:106).
+
+        ``ttl[m]`` is message m's hop limit (default: none), see ``set_ttl``.
 
         ``start_rounds[m]`` is the round message m originates in (default: all in round 0): in
         that round, after its arrivals, the origin makes a first receipt (hop = the round,
@@ -225,9 +228,33 @@ class GraphNetwork:
             self._check(_lib.lib().p2pg_set_sources_at(self._h, len(src), _lib.ptr(src), _lib.ptr(start)))
         self.sources = src
         self.start_rounds = start
+        self.ttl = np.full(len(src), -1, dtype=np.int32)  # (new sources carry no hop limits)
         self.rounds = []
         self.message_count_send = 0
         self._next_round, self._quiet = 0, False
+        if ttl is not None:
+            self.set_ttl(ttl)
+
+    def set_ttl(self, ttl):
+        """Hop limits, before round 0 runs (or after ``reset``): ``ttl[m] >= 0`` bounds broadcast
+        m, -1 leaves it unlimited; ``None`` removes them all.  A first receipt of m at relative hop
+        ``h = round - start_rounds[m]`` (the origination has h = 0) is recorded as always and
+        relays iff ``ttl[m] < 0 or h < ttl[m]`` -- the app that forwards ``ttl - 1`` while
+        ``ttl > 0`` (README.md:20); ``ttl = 0`` marks the message seen at its origin and sends
+        nothing.  ``reset`` keeps the limits, ``broadcast`` clears them (p2pg_set_ttl).  Read an
+        expiry round's ``deliveries()`` before its ``sends()`` / ``peer_counters()`` /
+        ``update_edges()`` / ``drop_relays()``."""
+        if self.sources is None:
+            raise RuntimeError("set_ttl: call broadcast(sources) first")
+        if ttl is None:
+            t = np.full(self.M, -1, dtype=np.int32)
+        else:
+            t = np.array(ttl, dtype=np.int64, ndmin=1)
+            if t.ndim != 1 or ((t < -(1 << 31)) | (t >= (1 << 31))).any():
+                raise ValueError("ttl must be a 1-D array of int32 hop limits")
+            t = np.ascontiguousarray(t, dtype=np.int32)
+        self._check(_lib.lib().p2pg_set_ttl(self._h, len(t), _lib.ptr(t) if ttl is not None else None))
+        self.ttl = t
 
     def originate(self, msgs, peers, round=None):
         """Between rounds: start the unscheduled broadcasts ``msgs`` at ``peers`` in ``round``
@@ -415,8 +442,10 @@ class GraphNetwork:
                                                 _lib.ptr(m) if len(m) else None))
         last = self.rounds[-1].round if self.rounds else -1
         origin = (self.start_rounds[m] == last).tolist()  # a message's own origination: all deg
-        drop = sum(min(self.fanout, d) if self.mode == "gossip" else (d if o else max(d - 1, 0))
-                   for d, o in zip(self.graph.degree()[p].tolist(), origin))
+        # (a receipt of a message whose hop limit ran out in that round made no relays)
+        spent = ((self.ttl[m] >= 0) & (self.start_rounds[m].astype(np.int64) + self.ttl[m] == last)).tolist()
+        drop = sum(0 if x else min(self.fanout, d) if self.mode == "gossip" else (d if o else max(d - 1, 0))
+                   for d, o, x in zip(self.graph.degree()[p].tolist(), origin, spent))
         self.message_count_send -= drop
 
     # -- validation planes ----------------------------------------------------------------
