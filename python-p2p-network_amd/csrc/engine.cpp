@@ -2009,11 +2009,12 @@ int p2pg_get_sends(p2pg_engine* e, int64_t cap, int32_t* sender, int32_t* receiv
   const int64_t c = cap > 0 ? cap : 1;
   int32_t *ds = nullptr, *dr = nullptr, *dm = nullptr;
   uint8_t* dl = nullptr;
-  HIPCHK(e, hipMalloc((void**)&ds, sizeof(int32_t) * c));
-  HIPCHK(e, hipMalloc((void**)&dr, sizeof(int32_t) * c));
-  HIPCHK(e, hipMalloc((void**)&dm, sizeof(int32_t) * c));
-  HIPCHK(e, hipMalloc((void**)&dl, c));
-  hipError_t lr = hipMemsetAsync(e->d_cnt2, 0, 2 * sizeof(unsigned long long), e->stream);
+  // (one chain: whatever fails, every buffer allocated so far is freed below)
+  hipError_t lr = hipMalloc((void**)&ds, sizeof(int32_t) * c);
+  if (lr == hipSuccess) lr = hipMalloc((void**)&dr, sizeof(int32_t) * c);
+  if (lr == hipSuccess) lr = hipMalloc((void**)&dm, sizeof(int32_t) * c);
+  if (lr == hipSuccess) lr = hipMalloc((void**)&dl, c);
+  if (lr == hipSuccess) lr = hipMemsetAsync(e->d_cnt2, 0, 2 * sizeof(unsigned long long), e->stream);
   if (lr == hipSuccess)
     lr = launch_sends(graph(e), graph_for_arrivals(e, r), e->st, p, true, cap, ds, dr, dm, dl, e->d_cnt2, e->stream);
   unsigned long long cnt = 0;
@@ -2133,14 +2134,13 @@ int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32
   if (lr == hipSuccess && count_lost_on(e))
     lr = enqueue_lost_count(e, graph(e), graph_for_arrivals(e, r), r);
   if (lr == hipSuccess) lr = hipStreamSynchronize(e->stream);
-  (void)hipFree(dl);
+  unsigned long long listed = 0;
+  if (lr == hipSuccess && gossip && e->wlist_check)
+    lr = hipMemcpy(&listed, e->st.stats + STAT_COUNT, sizeof(listed), hipMemcpyDeviceToHost);
+  (void)hipFree(dl);  // the one exit of the chain above: every path past the allocation frees it
   if (lr != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("drop_relays: ") + hipGetErrorString(lr));
   if (gossip) {
-    if (e->wlist_check) {
-      unsigned long long listed = 0;
-      HIPCHK(e, hipMemcpy(&listed, e->st.stats + STAT_COUNT, sizeof(listed), hipMemcpyDeviceToHost));
-      if ((rc = check_scatter_list(e, listed))) return rc;
-    }
+    if (e->wlist_check && (rc = check_scatter_list(e, listed))) return rc;
     e->consume_next = true;
     e->last_push_e = false;
     e->stats_clear = true;  // the re-push counted into the round counters
