@@ -155,6 +155,10 @@ int p2pg_gossip_targets(uint32_t round, uint32_t peer, uint32_t msg, uint32_t de
                         uint64_t seed, uint32_t* out);
 /* 1 iff a send over {a, b} made in round `round` is lost to churn.       */
 int p2pg_churn_lost(uint32_t round, uint32_t a, uint32_t b, uint32_t threshold, uint64_t seed);
+/* 1 iff the relay policy mutes the first receipt of message msg (global id) at peer in round
+ * `round` under the peer's threshold thr (p2pg_set_relay_policy; the exemption of originations is
+ * the caller's).                                                                            */
+int p2pg_relay_muted(uint32_t round, uint32_t peer, uint32_t msg, uint32_t thr, uint64_t seed);
 
 /* ---- engine ------------------------------------------------------------------------- */
 int p2pg_create(const p2pg_config* cfg, p2pg_engine** out);
@@ -213,6 +217,31 @@ int p2pg_originate(p2pg_engine* e, int64_t n, const int32_t* msg, const int32_t*
  * P2PG_PUSH_ATOMIC, and the next round's touched_words counts what that push touched (DESIGN.md
  * 4j).  Rounds without an expiry keep every form they have.                                    */
 int p2pg_set_ttl(p2pg_engine* e, int32_t M, const int32_t* ttl);
+/* Relay policy: the per-peer decision whether node_message forwards a first receipt
+ * (README.md:20, node.py:106-116) -- silent peers (free riders, light clients, faulty nodes) and
+ * probabilistic relay.  thr[v] = 0: peer v relays every first receipt; 0xFFFFFFFF: none; otherwise
+ * its first receipt of message m in round r is muted iff
+ *   philox4x32_10(ctr = (r, v, msg_id_base + m, 'RLY' = 0x00524C59), key = seed).x < thr[v]
+ * (p2pg_relay_muted evaluates it on the host; `seed` is the policy's own, independent of the
+ * gossip and churn seeds).  A muted first receipt behaves exactly like a receipt at its hop limit
+ * (p2pg_set_ttl): it happens as usual -- seen bit, hop, parent, every receipt counter, the delivery
+ * stream, the tallies -- and makes no sends: none in `relays`, the next round's `received`,
+ * p2pg_get_sends, p2pg_peer_counters or the lost-send count.  Originations (round 0's, a start
+ * round's, p2pg_originate's) are the app's own send_to_nodes and never muted; round 0 is never a
+ * policy round.  With hop limits a receipt sends iff it is neither expired nor muted.
+ * thr = NULL or all zero removes the policy: the engine then launches exactly what it launched
+ * before.  V = the engine's peer count (P2PG_ERR_ARG otherwise).  p2pg_reset keeps and replays the
+ * policy, p2pg_set_sources[_at] keep it (it belongs to the peers), p2pg_load_csr clears it.
+ * P2PG_ERR_STATE on a vertex-partitioned rank, between p2pg_step_begin / p2pg_step_end and once a
+ * round has run; while a policy is set p2pg_snapshot / p2pg_restore return P2PG_ERR_STATE.  A
+ * rejected call changes nothing.
+ * With a policy every round after round 0 is scheduled like an expiry round: the unfused
+ * schedule, and its sends become final at the points named for p2pg_set_ttl (read the round's
+ * deliveries first; p2pg_drop_relays of a muted receipt is legal and cancels nothing).  Its
+ * scatter_words is 0, the following round's touched_words counts what the held-back push
+ * touched, and push_form reports the form chosen for that push from the round's own density
+ * (P2PG_PUSH_ATOMIC or P2PG_PUSH_EDGE; P2PG_PUSH_ATOMIC in a round that is an expiry round too). */
+int p2pg_set_relay_policy(p2pg_engine* e, int64_t V, const uint32_t* thr, uint64_t seed);
 /* Back to round 0 with the same graph, sources and start rounds (clears seen/frontier state). */
 int p2pg_reset(p2pg_engine* e);
 /* One round. Returns 1 while messages are in flight, 0 when quiescent, < 0 on error. */

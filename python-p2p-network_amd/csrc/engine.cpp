@@ -22,6 +22,10 @@
 //                  expired first receipts leave its counters, and when its sends become final (the
 //                  next round's start or a boundary call) their frontier bits are cleared -- then,
 //                  gossip, its held-back push leaves by row atomics
+//   policy         with a relay policy (p2pg_set_relay_policy; relay_policy.hip) every round > 0 is
+//                  scheduled like an expiry round: the muted first receipts' relays leave its
+//                  counters, their frontier bits are cleared when its sends become final, and the
+//                  held-back gossip push then takes the form the round's own density chose
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +38,7 @@
 
 #include "../../include/p2pgpu.h"
 #include "internal.h"
+#include "philox.h"
 
 using namespace p2pg;
 
@@ -236,7 +241,21 @@ struct p2pg_engine {
   int32_t exp_pending = -1;      // the expiry round whose sends are not final yet: its expired
                                  // frontier bits still stand (they serve its delivery stream) and
                                  // its gossip push is held back (finalize_expiry)
-  int32_t exp_final = -1;        // the last expiry round whose frontier bits were cleared
+  int32_t exp_final = -1;        // the last expiry or policy round whose frontier bits were cleared
+  // Relay policy (p2pg_set_relay_policy): h_thr[v] = peer v's mute threshold (empty: no policy),
+  // d_thr its device copy, uploaded once.  The policy belongs to the peers: it lives and dies with
+  // the graph (p2pg_load_csr), not with the sources.  pex_rounds holds the rounds > 0 with an
+  // origination or an expiry, ascending, and d_pex one W-word mask per such round of the messages
+  // the policy leaves alone in it (relay_policy.hip); uploaded when the schedule, the hop limits
+  // or the policy change, not per round.
+  std::vector<uint32_t> h_thr;
+  uint32_t* d_thr = nullptr;
+  uint64_t pol_seed = 0;
+  bool pol_on = false;
+  std::vector<int32_t> pex_rounds;
+  uint64_t* d_pex = nullptr;
+  int32_t pol_pending = -1;      // the policy round whose sends are not final yet (finalize_expiry)
+  bool pol_push_e = false;       // ... and the form its held-back gossip push takes (edge stores)
 };
 
 namespace {
@@ -322,6 +341,9 @@ void free_state(p2pg_engine* e) {
   e->h_ttl.clear();
   e->ttl_on = false;
   e->exp_pending = e->exp_final = -1;
+  dfree(e->d_pex);  // (the policy itself stays with the graph: free_graph)
+  e->pex_rounds.clear();
+  e->pol_pending = -1;
   e->have_state = false;
 }
 
@@ -373,6 +395,9 @@ void free_graph(p2pg_engine* e) {
   dfree(e->d_send_seg);
   dfree(e->d_recv_seg);
   dfree(e->d_seg_cnt);
+  dfree(e->d_thr);
+  e->h_thr.clear();
+  e->pol_on = false;
   if (e->h_seg_cnt) (void)hipHostFree(e->h_seg_cnt);
   e->h_seg_cnt = nullptr;
   e->auto_buf = nullptr;
@@ -634,7 +659,8 @@ bool received_exact(const p2pg_engine* e) { return e->cfg.churn_threshold == 0 |
 bool tally_on(const p2pg_engine* e) { return (e->cfg.flags & P2PG_FLAG_TALLY) != 0; }
 // Does a round of this engine need its frontier rows whole (no skipped / partial rows, no
 // batched decay rounds)?
-bool frontier_needed(const p2pg_engine* e) { return count_lost_on(e) || tally_on(e); }
+// (a relay policy reads and rewrites the rows of every round: relay_policy.hip)
+bool frontier_needed(const p2pg_engine* e) { return count_lost_on(e) || tally_on(e) || e->pol_on; }
 
 // Enqueue the peer counters of the pending round (its sends are final now): the sends leave on
 // gs (gone slots = connections removed while they were in flight), the round's own arrivals
@@ -1109,6 +1135,64 @@ bool expires_in(const p2pg_engine* e, int32_t m, int32_t r) {
          (int64_t)e->h_start[m] + e->h_ttl[m] == (int64_t)r;
 }
 
+// Relay policy: the per-round masks of the messages the policy leaves alone -- the originations of
+// a round (the app's own send_to_nodes, not a relay) and the messages whose hop limit runs out in
+// it (k_expire cancels those, once).  One W-word mask per round > 0 that has either; round 0 is
+// never a policy round.  Runs when the schedule, the hop limits or the policy change.
+int upload_exempt(p2pg_engine* e) {
+  if (!e->have_state) return P2PG_OK;
+  const int32_t M = e->M, W = e->W;
+  std::vector<std::pair<int64_t, int32_t>> xs;  // (round, message)
+  for (int32_t m = 0; m < M && e->pol_on; ++m) {
+    if (e->h_start[m] < 0) continue;
+    if (e->h_start[m] > 0) xs.emplace_back(e->h_start[m], m);
+    if (!e->h_ttl.empty() && e->h_ttl[m] > 0) {  // (ttl 0 expires in the start round itself)
+      const int64_t x = (int64_t)e->h_start[m] + e->h_ttl[m];
+      if (x <= 0x7FFFFFFFll) xs.emplace_back(x, m);
+    }
+  }
+  std::sort(xs.begin(), xs.end());
+  e->pex_rounds.clear();
+  std::vector<uint64_t> masks;
+  for (const auto& xm : xs) {
+    if (e->pex_rounds.empty() || e->pex_rounds.back() != (int32_t)xm.first) {
+      e->pex_rounds.push_back((int32_t)xm.first);
+      masks.resize(masks.size() + (size_t)W, 0ull);
+    }
+    masks[masks.size() - (size_t)W + (xm.second >> 6)] |= 1ull << (xm.second & 63);
+  }
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  // (the stream may still run a pass that reads the old masks)
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  dfree(e->d_pex);
+  if (!masks.empty()) {
+    HIPCHK(e, hipMalloc((void**)&e->d_pex, sizeof(uint64_t) * masks.size()));
+    HIPCHK(e, hipMemcpy(e->d_pex, masks.data(), sizeof(uint64_t) * masks.size(), hipMemcpyHostToDevice));
+  }
+  return P2PG_OK;
+}
+
+// The policy's exempt mask of round r, or nullptr (no origination, no expiry in it).
+const uint64_t* exempt_mask(const p2pg_engine* e, int32_t r) {
+  if (e->pex_rounds.empty() || r > e->pex_rounds.back()) return nullptr;
+  auto it = std::lower_bound(e->pex_rounds.begin(), e->pex_rounds.end(), r);
+  if (it == e->pex_rounds.end() || *it != r) return nullptr;
+  return e->d_pex + (size_t)(it - e->pex_rounds.begin()) * e->W;
+}
+
+// Is the first receipt of message m at peer v in round r muted by the relay policy?
+bool policy_muted(const p2pg_engine* e, int64_t v, int32_t m, int32_t r) {
+  if (!e->pol_on || r <= 0 || e->h_start[m] == r) return false;
+  return relay_muted((uint32_t)r, (uint32_t)v, e->cfg.msg_id_base + (uint32_t)m, e->h_thr[v],
+                     (uint32_t)e->pol_seed, (uint32_t)(e->pol_seed >> 32));
+}
+
+// The sends of the pending expiry or policy round become final: its expired and its muted frontier
+// bits are cleared (relay_expire.hip, relay_policy.hip; a round may have both), then the rest as
+// for an expiry round.  A pure policy round's held-back gossip push takes the form the round chose
+// from its own counters (pol_push_e): row atomics as below, or edge-mask stores into E that the
+// next round pulls.  A round that is also an expiry round keeps the row atomics.
+//
 // The sends of the pending expiry round become final: its expired frontier bits are cleared
 // (from here on p2pg_get_new_deliveries refuses that round), then -- push -- a gossip round's
 // held-back pushes leave as row atomics into the planes the next round's update consumes (no
@@ -1120,28 +1204,45 @@ bool expires_in(const p2pg_engine* e, int32_t m, int32_t r) {
 // Returns a P2PG code.  The passes are timed with their classes: k_expire with the origination
 // class 0 (like k_originate, a pass over the schedule's messages), the push with class 2.
 int finalize_expiry(p2pg_engine* e, bool push) {
-  if (e->exp_pending < 0) return P2PG_OK;
-  const int32_t r = e->exp_pending;
-  const int64_t xi = expiry_index(e, r);
-  if (xi < 0) {
-    e->exp_pending = -1;
+  if (e->exp_pending < 0 && e->pol_pending < 0) return P2PG_OK;
+  const int32_t r = std::max(e->exp_pending, e->pol_pending);  // (both are the last round)
+  const int64_t xi = e->exp_pending >= 0 ? expiry_index(e, r) : -1;
+  const bool pol = e->pol_pending >= 0 && e->pol_on;
+  if (xi < 0 && !pol) {
+    e->exp_pending = e->pol_pending = -1;
     return P2PG_OK;
   }
   RoundParams p = params(e);
   p.round = r;
   const DevGraph g = graph(e);
-  const uint64_t* X = e->d_exp + 2 * (size_t)xi * e->W;
-  int rc = timed(e, 0, [&] { return launch_expire(g, e->st, p, X, X + e->W, true, e->stream); });
-  if (rc) return rc;
+  int rc;
+  if (xi >= 0) {
+    const uint64_t* X = e->d_exp + 2 * (size_t)xi * e->W;
+    if ((rc = timed(e, 0, [&] { return launch_expire(g, e->st, p, X, X + e->W, true, e->stream); }))) return rc;
+  }
+  if (pol &&
+      (rc = timed(e, 0, [&] {
+         return launch_policy(g, e->st, p, e->d_thr, e->pol_seed, exempt_mask(e, r), true, e->stream);
+       })))
+    return rc;
   // the bits are gone (stream order): the round is final whatever happens below
-  e->exp_pending = -1;
+  e->exp_pending = e->pol_pending = -1;
   e->exp_final = r;
   if (push && e->cfg.mode == P2PG_MODE_GOSSIP && e->last_new > 0) {
-    // The list is sized by the round's nonzero frontier words before the clearing (prev_aw), which
-    // bounds the words left after it: this push cannot outgrow its list, so its count is not read
-    // back (check_scatter_list would cost the boundary a host synchronisation).
-    rc = timed(e, 2, [&] { return launch_scatter_atomic(e, g, p, std::max<uint64_t>(e->prev_aw, 1)); });
-    e->wlist_check = false;
+    if (xi < 0 && e->pol_push_e) {
+      // a policy round that chose the dense form from its own counters: edge-mask stores into
+      // E[r&1], which the next round pulls (last_push_e stands since the round's end)
+      rc = timed(e, 6, [&] {
+        return launch_gossip_scatter(g, e->st, p, e->d_hub, e->n_hub, true, e->stream, e->d_hub_big,
+                                     e->n_hub_big, e->d_wide_big, e->n_wide_big);
+      });
+    } else {
+      // The list is sized by the round's nonzero frontier words before the clearing (prev_aw), which
+      // bounds the words left after it: this push cannot outgrow its list, so its count is not read
+      // back (check_scatter_list would cost the boundary a host synchronisation).
+      rc = timed(e, 2, [&] { return launch_scatter_atomic(e, g, p, std::max<uint64_t>(e->prev_aw, 1)); });
+      e->wlist_check = false;
+    }
     e->stats_clear = true;  // the push counted into the round counters
     if (rc) return rc;
   }
@@ -1191,6 +1292,8 @@ int set_sources(p2pg_engine* e, const char* what, int32_t M, const int32_t* src,
     e->h_ttl.clear();
     if ((rc = upload_expiry(e))) return rc;
   }
+  // (a relay policy belongs to the peers and stays: its exempt masks follow the new schedule)
+  if ((e->pol_on || e->d_pex) && (rc = upload_exempt(e))) return rc;
   return p2pg_reset(e);
 }
 
@@ -1235,6 +1338,7 @@ int p2pg_originate(p2pg_engine* e, int64_t n, const int32_t* msg, const int32_t*
   int rc = upload_schedule(e);
   if (rc) return rc;
   if (e->ttl_on && (rc = upload_expiry(e))) return rc;  // (the new starts fix their expiry rounds)
+  if (e->pol_on && (rc = upload_exempt(e))) return rc;  // (and the policy's exempt rounds)
   e->done = false;  // (an engine that had gone quiet runs on: a start lies ahead)
   return P2PG_OK;
 }
@@ -1259,7 +1363,46 @@ int p2pg_set_ttl(p2pg_engine* e, int32_t M, const int32_t* ttl) {
     e->h_ttl.assign(ttl, ttl + M);
   else
     e->h_ttl.clear();  // all -1 (or NULL): the engine without this call
-  return upload_expiry(e);
+  const int rc = upload_expiry(e);
+  return rc || !e->pol_on ? rc : upload_exempt(e);
+}
+
+int p2pg_set_relay_policy(p2pg_engine* e, int64_t V, const uint32_t* thr, uint64_t seed) {
+  if (!e) return fail(e, P2PG_ERR_ARG, "set_relay_policy: no engine");
+  if (!e->d_rowptr) return fail(e, P2PG_ERR_STATE, "set_relay_policy: load a graph first");
+  if (V != e->V) return fail(e, P2PG_ERR_ARG, "set_relay_policy: V differs from the engine's peer count");
+  if (partitioned(e))
+    return fail(e, P2PG_ERR_STATE, "set_relay_policy: a relay policy is not available on a vertex-partitioned rank");
+  if (e->begun) return fail(e, P2PG_ERR_STATE, "set_relay_policy: a round has begun (step_begin)");
+  if (e->have_state && e->round > 0)
+    return fail(e, P2PG_ERR_STATE, "set_relay_policy: a round has run (set the policy before round 0, or after p2pg_reset)");
+  if (!e->failed.empty()) return fail(e, P2PG_ERR_STATE, "set_relay_policy: " + e->failed);
+  bool any = false;
+  for (int64_t v = 0; thr && v < V; ++v) any |= thr[v] != 0u;
+  if (!any && !e->pol_on) return P2PG_OK;  // nothing set, nothing to remove
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (any) {
+    uint32_t* d = nullptr;
+    HIPCHK(e, hipMalloc((void**)&d, sizeof(uint32_t) * (size_t)V));
+    const hipError_t x = hipMemcpy(d, thr, sizeof(uint32_t) * (size_t)V, hipMemcpyHostToDevice);
+    if (x != hipSuccess) {
+      (void)hipFree(d);
+      return fail(e, P2PG_ERR_HIP, std::string("set_relay_policy: ") + hipGetErrorString(x));
+    }
+    dfree(e->d_thr);
+    e->d_thr = d;
+    e->h_thr.assign(thr, thr + V);
+    e->pol_seed = seed;
+    e->pol_on = true;
+  } else {  // all zero (or NULL): the engine without this call
+    dfree(e->d_thr);
+    e->h_thr.clear();
+    e->pol_seed = 0;
+    e->pol_on = false;
+  }
+  e->pol_pending = -1;
+  return upload_exempt(e);
 }
 
 }  // extern "C"
@@ -1384,6 +1527,7 @@ int p2pg_reset(p2pg_engine* e) {
   e->tally_pending = -1;
   e->tally_read_at = -1;
   e->exp_pending = e->exp_final = -1;  // (the hop limits themselves stay and are replayed)
+  e->pol_pending = -1;                 // (and so does the relay policy)
   e->round = 0;
   e->done = false;
   e->failed.clear();
@@ -1500,7 +1644,11 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   // whole frontier rows, which the correction pass and the boundary's clearing read and write
   // (relay_expire.hip); its gossip push is held back until its sends are final (finalize_expiry).
   const int64_t xi = expiry_index(e, e->round);
-  const bool plain = orig != nullptr || xi >= 0;
+  // With a relay policy (p2pg_set_relay_policy) every round after round 0 is: any of its first
+  // receipts may be muted (relay_policy.hip), and its gossip push is held back in the same way --
+  // in the form chosen below from the round's own counters.
+  const bool pol = e->pol_on && e->round > 0;
+  const bool plain = orig != nullptr || xi >= 0 || pol;
   // the update / pull-only pass of this round (fused and update+push rounds set their own)
   if (gossip && !plain && partial_frontier(e, e->skip_frontier)) p.store_f = 2;
   uint64_t host_new = 0, host_relays = 0, host_av = 0, host_aw = 0, host_wedge = 0, host_degact = 0;
@@ -1588,9 +1736,10 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   };
   if (gossip && (fused_round || up_round)) {
     e->last_push_e = true;  // the fused launches pushed every source of this round
-  } else if (gossip && xi >= 0) {
+  } else if (gossip && (xi >= 0 || pol)) {
     // an expiry round: its pushes wait until the expired frontier bits are cleared, when its sends
-    // become final (finalize_expiry: row atomics into the planes the next round's update consumes)
+    // become final (finalize_expiry: row atomics into the planes the next round's update consumes).
+    // A policy round's wait alike; its form is chosen at the round's end (below)
     e->last_push_e = false;
   } else if (gossip) {
     // push form for this round's sends: row atomics when the frontier is sparse, whole-row
@@ -1682,8 +1831,18 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     }
     e->exp_pending = e->round;
   }
-  // (an expiry round's lost sends are counted once its expired bits are cleared: finalize_expiry)
-  const bool cnt_lost = count_lost_on(e) && xi < 0;
+  if (pol) {
+    // relay policy: the muted first receipts' relays leave this round's total as well (never an
+    // origination's, never twice for a receipt a hop limit cancelled: the round's exempt mask)
+    if ((rc = timed(e, 0, [&] {
+           return launch_policy(g, s, p, e->d_thr, e->pol_seed, exempt_mask(e, e->round), false, e->stream);
+         })))
+      return rc;
+    e->pol_pending = e->round;
+    e->pol_push_e = false;
+  }
+  // (an expiry or policy round's lost sends are counted once its bits are cleared: finalize_expiry)
+  const bool cnt_lost = count_lost_on(e) && xi < 0 && !pol;
   if (cnt_lost) {  // this round's lost sends: the next round's arrivals are its sends minus them
     hipError_t x = enqueue_lost_count(e, g, graph_for_arrivals(e, e->round), e->round);
     if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("step (lost sends): ") + hipGetErrorString(x));
@@ -1691,6 +1850,16 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   if ((rc = read_stats())) return rc;
   std::memcpy(e->stats_base, e->h_stats, sizeof(e->stats_base));  // the next round counts from here
   if ((rc = check_scatter_list(e, e->h_stats[STAT_COUNT]))) return rc;
+  if (gossip && pol && xi < 0 && s.E[0]) {
+    // the form of this policy round's held-back push, by the rule of the rounds that push at once
+    // (P2PG_GOSSIP_PUSH; auto: the density of the round's own frontier, before the muting).  A
+    // dense round by row atomics only would run at the atomic units' rate
+    e->pol_push_e = e->push_mode == 2 ||
+                    (e->push_mode == 0 && tot[ST_ACTIVE_V] > 0 &&
+                     (double)tot[ST_ACTIVE_W] >= e->e_thresh * (double)tot[ST_ACTIVE_V] * (double)e->W &&
+                     (double)tot[ST_ACTIVE_V] >= e->v_thresh * (double)e->v_conn);
+    e->last_push_e = e->pol_push_e;  // (the next round pulls E; push_form reports it)
+  }
   if (e->auto_round == e->round)  // the round's own pack landed with its counters
     for (int q = 0; q + 1 < (int)e->send_seg.size(); ++q) e->auto_cnt[q] = (int64_t)e->h_seg_cnt[q];
 #ifdef P2PG_PROF
@@ -1917,7 +2086,7 @@ int p2pg_get_new_deliveries(p2pg_engine* e, int64_t cap, int32_t* peer, int32_t*
   if (!e->frontier_kept)
     return fail(e, P2PG_ERR_STATE, "get_new_deliveries: the last round's frontier was not kept");
   if (e->exp_final == e->round - 1)
-    return fail(e, P2PG_ERR_STATE, "get_new_deliveries: hop limits expired in the last round and its sends were "
+    return fail(e, P2PG_ERR_STATE, "get_new_deliveries: hop limits expired or a relay policy acted in the last round and its sends were "
                                    "made final (get_sends, peer_counters, update_edges, drop_relays or "
                                    "step_begin): read the round's deliveries first");
   if (!e->frontier_kept_prev)
@@ -2083,7 +2252,11 @@ int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32
   // such an entry can no longer be checked against them: it is then taken as listed.
   if (e->exp_final == r)
     list.erase(std::remove_if(list.begin(), list.end(),
-                              [&](uint64_t x) { return expires_in(e, (int32_t)(uint32_t)x, r); }),
+                              [&](uint64_t x) {
+                                // (a receipt the relay policy muted went the same way)
+                                return expires_in(e, (int32_t)(uint32_t)x, r) ||
+                                       policy_muted(e, (int64_t)(x >> 32), (int32_t)(uint32_t)x, r);
+                              }),
                list.end());
   n = (int64_t)list.size();
   uint64_t* dl = nullptr;
@@ -2117,6 +2290,7 @@ int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32
     const uint64_t deg = (uint64_t)(e->h_rowptr[v + 1] - e->h_rowptr[v]);
     const bool origin = e->h_start[(uint32_t)list[i]] == r;  // the message's own origination
     if (expires_in(e, (int32_t)(uint32_t)list[i], r)) continue;  // (it made no relays to cancel)
+    if (policy_muted(e, v, (int32_t)(uint32_t)list[i], r)) continue;  // (nor did a muted receipt)
     cancelled += gossip ? std::min<uint64_t>(deg, (uint64_t)e->cfg.fanout) : (origin ? deg : (deg ? deg - 1 : 0));
   }
   if (lr == hipSuccess && gossip) {
@@ -2265,6 +2439,9 @@ int p2pg_set_global_ids(p2pg_engine* e, const int32_t* gid) {
                                    "vertex-partitioned rank");
   if (gid && e->have_state && e->ttl_on)
     return fail(e, P2PG_ERR_STATE, "set_global_ids: hop limits (p2pg_set_ttl) are not available on a "
+                                   "vertex-partitioned rank");
+  if (gid && e->pol_on)
+    return fail(e, P2PG_ERR_STATE, "set_global_ids: a relay policy (p2pg_set_relay_policy) is not available on a "
                                    "vertex-partitioned rank");
   HIPCHK(e, hipSetDevice(e->cfg.device));
   dfree(e->d_gid);
@@ -2730,6 +2907,8 @@ int p2pg_snapshot(p2pg_engine* e, void* buf, int64_t cap) {
                                    "(p2pg_set_sources_at / p2pg_originate)");
   if (e->ttl_on)
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold hop limits (p2pg_set_ttl)");
+  if (e->pol_on)
+    return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold a relay policy (p2pg_set_relay_policy)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "snapshot: a round has begun (step_begin)");
   if (e->arr_round >= 0 && e->arr_round == e->round)
     return fail(e, P2PG_ERR_STATE, "snapshot: take it before a topology update or after the next round");
@@ -2798,6 +2977,8 @@ int p2pg_restore(p2pg_engine* e, const void* buf, int64_t size) {
                                    "(p2pg_set_sources_at / p2pg_originate)");
   if (e->ttl_on)
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold hop limits (p2pg_set_ttl)");
+  if (e->pol_on)
+    return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold a relay policy (p2pg_set_relay_policy)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "restore: a round has begun (step_begin)");
   SnapHeader h;
   std::memcpy(&h, buf, sizeof(h));

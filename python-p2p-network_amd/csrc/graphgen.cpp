@@ -395,6 +395,10 @@ int p2pg_churn_lost(uint32_t round, uint32_t a, uint32_t b, uint32_t threshold, 
   return churn_dropped(round, a, b, threshold, (uint32_t)seed, (uint32_t)(seed >> 32)) ? 1 : 0;
 }
 
+int p2pg_relay_muted(uint32_t round, uint32_t peer, uint32_t msg, uint32_t thr, uint64_t seed) {
+  return relay_muted(round, peer, msg, thr, (uint32_t)seed, (uint32_t)(seed >> 32)) ? 1 : 0;
+}
+
 const char* p2pg_global_error(void) { return g_error.c_str(); }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 //   sources : key = (seed_lo, seed_hi ^ TAG_SRC), ctr = (msg_global, 0, 0, 0)
 //   gossip  : key = (seed_lo, seed_hi),           ctr = (round, peer, msg_global, TAG_GSP | blk<<24)
 //   churn   : key = (seed_lo, seed_hi),           ctr = (round, min(a,b), max(a,b), TAG_CHN)
+//   policy  : key = (seed_lo, seed_hi),           ctr = (round, peer, msg_global, TAG_RLY)
 #pragma once
 #include <stdint.h>
 
@@ -28,6 +29,7 @@ constexpr uint32_t PHILOX_W1 = 0xBB67AE85u;
 constexpr uint32_t TAG_SRC = 0x00535243u;  // 'SRC'
 constexpr uint32_t TAG_GSP = 0x00475350u;  // 'GSP'
 constexpr uint32_t TAG_CHN = 0x0043484Eu;  // 'CHN'
+constexpr uint32_t TAG_RLY = 0x00524C59u;  // 'RLY' relay policy
 constexpr uint32_t TAG_RRG = 0x00525247u;  // 'RRG' random-regular generator
 constexpr uint32_t TAG_GNP = 0x00474E50u;  // 'GNP'
 constexpr uint32_t TAG_BAG = 0x00424147u;  // 'BAG' Barabasi-Albert generator
@@ -207,6 +209,17 @@ P2PG_HD bool churn_dropped(uint32_t round, uint32_t a, uint32_t b, uint32_t thre
   if (threshold == 0u) return false;
   const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
   u32x4 c = {round, lo, hi, TAG_CHN};
+  return philox4x32_10(c, seed_lo, seed_hi).x < threshold;
+}
+
+// Relay policy (p2pg_set_relay_policy): the first receipt of message msg (global id) at peer in
+// round `round` is muted -- it happens and sends nothing -- iff the first Philox word is below the
+// peer's threshold; 0 never draws (relays all), 0xFFFFFFFF never draws (relays none).
+P2PG_HD bool relay_muted(uint32_t round, uint32_t peer, uint32_t msg, uint32_t threshold,
+                         uint32_t seed_lo, uint32_t seed_hi) {
+  if (threshold == 0u) return false;
+  if (threshold == 0xFFFFFFFFu) return true;
+  u32x4 c = {round, peer, msg, TAG_RLY};
   return philox4x32_10(c, seed_lo, seed_hi).x < threshold;
 }
 

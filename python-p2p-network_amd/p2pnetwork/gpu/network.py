@@ -162,6 +162,8 @@ class GraphNetwork:
         self.sources = None
         self.start_rounds = None     # int32 [M]: the round each broadcast originates in (-1 = unscheduled)
         self.ttl = None              # int32 [M]: each broadcast's hop limit (-1 = unlimited)
+        self.relay_thr = None        # uint32 [V]: the relay policy's mute thresholds (None = no policy)
+        self.relay_seed = 0
         self._autostop = bool(autostop)
         self._next_round = 0         # the next round the engine runs
         self._quiet = False          # the engine went quiet (further steps run no round)
@@ -255,6 +257,54 @@ class GraphNetwork:
             t = np.ascontiguousarray(t, dtype=np.int32)
         self._check(_lib.lib().p2pg_set_ttl(self._h, len(t), _lib.ptr(t) if ttl is not None else None))
         self.ttl = t
+
+    @staticmethod
+    def relay_thresholds(relay_prob, V):
+        """uint32 [V] mute thresholds of relay probabilities q in [0, 1] (scalar or [V]):
+        1 -> 0 (relays all, no draw), 0 -> 0xFFFFFFFF (relays none, no draw), otherwise
+        floor((1 - q) * 2^32) clipped to [1, 0xFFFFFFFE]."""
+        q = np.asarray(relay_prob, dtype=np.float64)
+        if q.ndim > 1 or (q.ndim == 1 and len(q) != V):
+            raise ValueError("relay_prob must be a scalar or one probability per peer")
+        q = np.broadcast_to(q, (V,))
+        if not ((q >= 0.0) & (q <= 1.0)).all():
+            raise ValueError("relay probabilities must lie in [0, 1]")
+        t = np.clip(np.floor((1.0 - q) * 4294967296.0), 1.0, float(0xFFFFFFFE))
+        t = np.where(q == 1.0, 0.0, np.where(q == 0.0, float(0xFFFFFFFF), t))
+        return np.ascontiguousarray(t, dtype=np.uint32)
+
+    @staticmethod
+    def relay_muted(round, peer, msg, threshold, seed=0):
+        """Does the relay policy mute the first receipt of message ``msg`` (global id) at ``peer``
+        in ``round`` under the peer's ``threshold``?  (p2pg_relay_muted; originations are exempt,
+        which is the caller's to apply.)"""
+        return bool(_lib.lib().p2pg_relay_muted(int(round), int(peer), int(msg), int(threshold), int(seed)))
+
+    def set_relay_policy(self, relay_prob=None, *, thresholds=None, seed=0):
+        """Per-peer relay policy, before round 0 runs (or after ``reset``): peer v forwards a first
+        receipt with probability ``relay_prob[v]`` (scalar or [V]; 0 = a silent peer that receives
+        and never forwards, 1 = always).  A muted receipt is recorded as always and sends nothing,
+        like a receipt at its hop limit; originations are never muted.  ``thresholds`` gives the
+        uint32 [V] thresholds directly (see ``relay_thresholds``); ``seed`` is the policy's own
+        Philox key.  ``None`` (or probability 1 everywhere) removes the policy.  ``reset`` and
+        ``broadcast`` keep it (p2pg_set_relay_policy).  Read a round's ``deliveries()`` before its
+        ``sends()`` / ``peer_counters()`` / ``update_edges()`` / ``drop_relays()``."""
+        V = self.graph.V
+        if relay_prob is not None and thresholds is not None:
+            raise ValueError("give relay_prob or thresholds, not both")
+        if thresholds is not None:
+            t = np.array(thresholds, dtype=np.int64, ndmin=1)
+            if t.shape != (V,) or ((t < 0) | (t > 0xFFFFFFFF)).any():
+                raise ValueError("thresholds must be one uint32 per peer")
+            t = np.ascontiguousarray(t, dtype=np.uint32)
+        elif relay_prob is not None:
+            t = self.relay_thresholds(relay_prob, V)
+        else:
+            t = None
+        self._check(_lib.lib().p2pg_set_relay_policy(self._h, V, _lib.ptr(t) if t is not None else None,
+                                                     ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)))
+        self.relay_thr = t if t is not None and t.any() else None
+        self.relay_seed = int(seed) & 0xFFFFFFFFFFFFFFFF if self.relay_thr is not None else 0
 
     def originate(self, msgs, peers, round=None):
         """Between rounds: start the unscheduled broadcasts ``msgs`` at ``peers`` in ``round``
@@ -444,6 +494,10 @@ class GraphNetwork:
         origin = (self.start_rounds[m] == last).tolist()  # a message's own origination: all deg
         # (a receipt of a message whose hop limit ran out in that round made no relays)
         spent = ((self.ttl[m] >= 0) & (self.start_rounds[m].astype(np.int64) + self.ttl[m] == last)).tolist()
+        if self.relay_thr is not None and last > 0:  # (nor did one the relay policy muted)
+            base = int(self.config.msg_id_base)
+            spent = [x or (not o and self.relay_muted(last, v, base + k, int(self.relay_thr[v]), self.relay_seed))
+                     for x, o, v, k in zip(spent, origin, p.tolist(), m.tolist())]
         drop = sum(0 if x else min(self.fanout, d) if self.mode == "gossip" else (d if o else max(d - 1, 0))
                    for d, o, x in zip(self.graph.degree()[p].tolist(), origin, spent))
         self.message_count_send -= drop
