@@ -39,8 +39,10 @@
 #include "../../include/p2pgpu.h"
 #include "internal.h"
 #include "philox.h"
+#include "round_plan.h"
 
 using namespace p2pg;
+namespace rp = round_plan;
 
 // round 0's counters (seed_stats)
 struct SeedStats {
@@ -52,9 +54,6 @@ struct p2pg_engine {
   p2pg_config cfg{};
   std::string err;
   int64_t V = 0, nnz = 0;
-  int64_t v_conn = 0;          // peers with >= 1 connection: the ones a round can make active
-                               // (the dense-round test compares active peers with these, so
-                               // isolated peers do not keep a run sparse)
   int32_t M = 0, W = 0;
   std::vector<int64_t> h_rowptr;
   std::vector<int32_t> h_colidx;  // host copy of the adjacency (topology updates, snapshots)
@@ -99,22 +98,18 @@ struct p2pg_engine {
   int64_t auto_cnt[P2PG_MAX_RANKS] = {0};  // their counts per destination (h_seg_cnt is reused
                                            // by explicit packs of the other plane)
   bool begun = false;                 // p2pg_step_begin ran this round's phase 0
-  bool last_push_e = false;    // gossip: pushes of the previous round went to E (dense)
-  double e_thresh = 0.06;      // store-mode when active words >= thresh * active rows * W;
+  // the round schedule (round_plan.h): the rolling counters of the finished rounds and the rules
+  // (row width and thresholds: alloc_state; v_conn: p2pg_load_csr; the switches: p2pg_create)
+  rp::RoundHistory hist;
+  rp::RoundRules rules;
   double e_thresh_env = -1.0;  // P2PG_E_THRESH (>= 0) or by the current row width (alloc_state)
                                // (c4 A/B, interleaved runs: 0.04 320.4 ms vs 0.1 324.3 ms, round 1;
                                // with the lane-parallel sparse push (round 2) W = 64: 0.04 / 0.06 /
                                // 0.08 -> 278.4 / 275.5 / 275.2 ms, W = 8: 89.1 / 89.4 / 89.5 ms)
-  double v_thresh = 0.3;       // ... and active rows >= v_thresh * v_conn (by row width, alloc_state;
-  double v_thresh_env = -1.0;  // P2PG_V_THRESH overrides): a dense round visits every
-                               // unsaturated peer, a sparse one only the pushed-to rows (narrow
-                               // rows: word density alone is high whenever anything is active)
-  int push_mode = 0;           // 0 auto, 1 always row atomics, 2 always edge stores
+  double v_thresh_env = -1.0;  // P2PG_V_THRESH, likewise
   bool fused = true;           // dense rounds after dense rounds: one pull+scatter pass
   bool wide_atomic = true;     // fused rounds: hub pushes by atomics (P2PG_WIDE_ATOMIC=0: one
                                // wave per 16-connection chunk item)
-  int push_dedup = -1;         // sparse pushes drop seen bits: -1 in the decay phase, 0 never,
-                               // 1 always (P2PG_PUSH_DEDUP)
   bool sparse_lp = true;       // sparse rounds: lane-parallel scatter (relay_sparse.hip) when
                                // the rows allow it; P2PG_SPARSE_LP=0 keeps the per-source one
   bool skip_frontier = false;  // p2pg_run, not its last two allowed rounds: fused rounds may skip F
@@ -122,18 +117,6 @@ struct p2pg_engine {
                                // only (P2PG_PARTIAL_F=0: whole rows, A/B)
   bool frontier_kept = true;   // F[(round-1)&1] holds the last round's first receipts
   bool frontier_kept_prev = true;  // ... and F[round&1] the round before (delivery parents)
-  uint64_t prev_aw = 0, prev_av = 0;  // active words / rows of the previous round
-  uint64_t last_new = 0;       // first receipts of the last round run
-  uint64_t prev2_aw = 0, prev2_av = 0, prev2_new = 0;  // the same, one round earlier
-  uint64_t prev_sw = 0;        // distinct masks pushed in the last round (>= the next frontier's
-                               // nonzero words: each of them received at least one)
-  bool saw_dense = false;      // a round of this run pushed into E (the dense phase has begun)
-  bool decay_pred = true;      // still_dense shrinks the counters in the decay phase
-                               // (P2PG_DECAY_PRED=0: the last round's counters as they are)
-  int update_push = -1;        // the first dense round after a sparse one: its update and its
-                               // E pushes in one pass (launch_gossip_update_push) -- -1 when the
-                               // round is predicted dense (predict_dense), 0 never, 1 whenever
-                               // the rows allow it (P2PG_UPDATE_PUSH)
   int32_t* d_src = nullptr;
   DevState st{};
   size_t plane_bytes = 0, bm_bytes = 0;
@@ -255,7 +238,8 @@ struct p2pg_engine {
   std::vector<int32_t> pex_rounds;
   uint64_t* d_pex = nullptr;
   int32_t pol_pending = -1;      // the policy round whose sends are not final yet (finalize_expiry)
-  bool pol_push_e = false;       // ... and the form its held-back gossip push takes (edge stores)
+  bool held_push_e = false;      // the pending round's held-back gossip push leaves by edge stores
+                                 // (rp::resolve_push at its end), not by row atomics
 };
 
 namespace {
@@ -544,63 +528,13 @@ bool wide_atomic_on(const p2pg_engine* e) {
   return e->wide_atomic && e->W <= 64 && (e->W <= PACK_W_MAX_PLAIN || e->st.AW[0]);
 }
 
-// Will the pushes of round e->round (a round after a sparse one, before its update ran) be dense
-// by the rule the engine applies to its own stats (use_e below)?  Rising phase only: active words
-// grow by the last round's factor and inactive peers shrink by it, with a 15 % margin on the word
-// test.  On config 4's recorded rounds at 512 / 1024 / 2048 / 4096 broadcasts this names exactly
-// the first dense round at W = 32 / 64 and none at W <= 16 (no false positive).  A wrong guess
-// changes the push form of one round, never a result.
-bool predict_dense(const p2pg_engine* e) {
-  if (e->prev2_aw == 0 || e->prev2_av == 0 || e->last_new <= e->prev2_new) return false;
-  const double V = (double)e->v_conn;
-  const double in1 = V - (double)e->prev_av, in2 = V - (double)e->prev2_av;
-  if (in2 <= 0.0) return false;
-  const double est_av = V - in1 * (in1 / in2);
-  const double est_aw = (double)e->prev_aw * ((double)e->prev_aw / (double)e->prev2_aw);
-  return est_av > 0.0 && est_aw >= 1.15 * e->e_thresh * est_av * (double)e->W &&
-         est_av >= e->v_thresh * V;
-}
-
-// Will this round's pushes go by row atomics whatever its counters say?  Then the push is
-// launched without reading them first (one host synchronisation per round instead of two): in
-// the decay phase (after the dense rounds, receipts shrinking) and while the rising frontier is
-// far below the dense-round thresholds (active peers, grown twice by the last growth factor, under
-// half of v_thresh * v_conn).  Only the push form depends on it, never a result.
-bool clearly_sparse(const p2pg_engine* e) {
-  if (e->round == 0) return false;  // (origination: the counters are the host's)
-  // a bound, not a guess: every active peer of this round received at least one of the masks
-  // pushed in the last one (prev_sw), and a dense round needs v_thresh * v_conn active peers
-  // (c4: rounds 5 and 6, whose frontiers grow too fast for the guess below)
-  if (e->prev_sw > 0 && (double)e->prev_sw < e->v_thresh * (double)e->v_conn) return true;
-  if (e->saw_dense) return e->last_new < e->prev2_new;
-  if (e->prev_av == 0) return true;  // nothing arrives: an empty round
-  const double grow = e->prev2_av ? std::max(1.0, (double)e->prev_av / (double)e->prev2_av) : 64.0;
-  return (double)e->prev_av * grow * grow < 0.5 * e->v_thresh * (double)e->v_conn;
-}
-
-// A dense round follows a dense round if the frontier it will push is still dense by the rule
-// the engine applies to its own counters (use_e in p2pg_step).  The counters are those of the
-// round before; in the decay phase (receipts shrinking) they are first shrunk by their last
-// factor, so the last dense round is not one round late (c4: round 24's 3.0e7 active words are
-// below 0.06 x 8.2e6 peers x 64, while round 23's were above).  Only the push form depends on
-// it, never a result.
-bool still_dense(const p2pg_engine* e) {
-  double aw = (double)e->prev_aw, av = (double)e->prev_av;
-  if (e->decay_pred && e->saw_dense && e->last_new < e->prev2_new && e->prev2_aw && e->prev2_av) {
-    aw *= aw / (double)e->prev2_aw;
-    av *= av / (double)e->prev2_av;
-  }
-  return av > 0.0 && aw >= e->e_thresh * av * (double)e->W && av >= e->v_thresh * (double)e->v_conn;
-}
-
-// Inside p2pg_run (not its last two allowed rounds, no hop/parent records): may this round's update
-// / last dense pull write only the nonzero words of its frontier rows (RoundParams::store_f == 2)?
-// Packed rows only (16 < W <= 64: AW planes, one peer per wave), not on a partitioned rank.  A
+// May a round inside p2pg_run (not its last two allowed rounds) write only the nonzero words of its
+// frontier rows in its update / last dense pull (RoundParams::store_f == 2)?  No hop/parent records,
+// packed rows only (16 < W <= 64: AW planes, one peer per wave), not on a partitioned rank.  A
 // whole 512 B row write per active peer was ~40 % of the sparse update's bytes; the words are
 // read back only through the AW mask (sparse push list, push-only pass, per-source scatter).
-bool partial_frontier(const p2pg_engine* e, bool skip) {
-  return skip && !e->st.hop && e->st.AW[0] && e->W > GROUPED_W_MAX && e->W <= 64 && !e->d_gid &&
-         e->partial_f;
+bool partial_rows(const p2pg_engine* e) {
+  return !e->st.hop && e->st.AW[0] && e->W > GROUPED_W_MAX && e->W <= 64 && !e->d_gid && e->partial_f;
 }
 
 // A fused dense round (pull of E[(r-1)&1] + pushes into E[r&1]) and its hub pushes.
@@ -626,12 +560,19 @@ bool part_dense(const p2pg_engine* e) {
          e->W > GROUPED_W_MAX && e->W <= 64;
 }
 
-// Run this round's update and its (dense) pushes in one pass?
-bool update_push_round(const p2pg_engine* e, const RoundParams& p) {
-  if (e->update_push == 0 || e->cfg.mode != P2PG_MODE_GOSSIP || e->push_mode != 0 || e->d_gid ||
-      p.phase >= 0 || !e->st.E[0] || !wide_atomic_on(e) || !gossip_update_push_supported(e->st))
-    return false;
-  return e->update_push == 1 || predict_dense(e);
+// What this engine's state and kernels allow a round (round_plan.h), evaluated once per round.
+rp::RoundCaps round_caps(const p2pg_engine* e) {
+  rp::RoundCaps c;
+  c.gossip = e->cfg.mode == P2PG_MODE_GOSSIP;
+  c.e_planes = e->st.E[0] != nullptr;
+  c.partitioned = e->d_gid != nullptr;
+  c.part_dense = part_dense(e);
+  c.fused = gossip_fused_supported(e->st);
+  c.update_push = gossip_update_push_supported(e->st) && wide_atomic_on(e);
+  c.sparse_scatter = sparse_scatter_on(e);
+  c.partial_rows = partial_rows(e);
+  c.records = e->st.hop != nullptr;
+  return c;
 }
 
 // After the stream synced on a round whose push ran lane-parallel: the list must have held
@@ -696,7 +637,7 @@ int alloc_edge_planes(p2pg_engine* e) {
   if (s.E[1] == s.E[0]) s.E[1] = nullptr;
   dfree(s.E[0]);
   dfree(s.E[1]);
-  if (e->cfg.mode != P2PG_MODE_GOSSIP || !e->d_rev || e->push_mode == 1) return P2PG_OK;
+  if (e->cfg.mode != P2PG_MODE_GOSSIP || !e->d_rev || e->rules.push_mode == 1) return P2PG_OK;
   // a rank-local graph's ghost slots are usable by the PART kernels only (part_dense)
   if ((e->cfg.flags & P2PG_FLAG_LOCAL_GRAPH) &&
       !(e->fused && e->W > GROUPED_W_MAX && e->W <= 64 && s.AW[0]))
@@ -716,15 +657,15 @@ int alloc_edge_planes(p2pg_engine* e) {
 int alloc_state(p2pg_engine* e) {
   free_state(e);
   DevState& s = e->st;
-  s.W = e->W;
-  e->e_thresh = e->e_thresh_env >= 0.0 ? e->e_thresh_env : (e->W > GROUPED_W_MAX ? 0.06 : 0.04);
+  s.W = e->rules.W = e->W;
+  e->rules.e_thresh = e->e_thresh_env >= 0.0 ? e->e_thresh_env : (e->W > GROUPED_W_MAX ? 0.06 : 0.04);
   // a dense round costs a visit of every unsaturated peer whatever the width, a sparse one an
   // atomic per pushed mask: narrow rows (a message split's shares) stay sparse until nearly every
   // peer is active (c4 interleaved sweeps, profiles/r03/ab_v_thresh.txt: W = 8 0.3 / 0.6 / 0.9 /
   // 0.95 / 0.98 -> 85.6 / 81.3 / 79.9 / 79.2 / 83.6 ms; W = 16 -> 144.5 / 138.9 / 130.4 / 128.7 /
   // 127.6 ms; W = 32 0.3 / 0.7 / 0.9 / 0.95 -> 218.4 / 211.7 / 208.4 / 203.7 ms; W = 64: 0.3 ...
   // 0.9 equal, 0.95 within 1 %, so the round-2 value stays)
-  e->v_thresh = e->v_thresh_env >= 0.0 ? e->v_thresh_env : e->W <= 32 ? 0.95 : 0.3;
+  e->rules.v_thresh = e->v_thresh_env >= 0.0 ? e->v_thresh_env : e->W <= 32 ? 0.95 : 0.3;
   s.M = e->M;
   e->plane_bytes = (size_t)e->V * e->W * sizeof(uint64_t);
   e->seen_spare_off = false;  // a new plane size: the spare's size / memory check runs again
@@ -818,15 +759,15 @@ int p2pg_create(const p2pg_config* cfg, p2pg_engine** out) {
   if (const char* t = std::getenv("P2PG_V_THRESH")) e->v_thresh_env = std::atof(t);
   if (const char* f = std::getenv("P2PG_FUSED")) e->fused = std::strcmp(f, "0") != 0;
   if (const char* f = std::getenv("P2PG_SPARSE_LP")) e->sparse_lp = std::strcmp(f, "0") != 0;
-  if (const char* f = std::getenv("P2PG_PUSH_DEDUP")) e->push_dedup = std::atoi(f);
+  if (const char* f = std::getenv("P2PG_PUSH_DEDUP")) e->rules.push_dedup = std::atoi(f);
   if (const char* f = std::getenv("P2PG_WIDE_ATOMIC")) e->wide_atomic = std::strcmp(f, "0") != 0;
-  if (const char* f = std::getenv("P2PG_UPDATE_PUSH")) e->update_push = std::atoi(f);
+  if (const char* f = std::getenv("P2PG_UPDATE_PUSH")) e->rules.update_push = std::atoi(f);
   if (const char* f = std::getenv("P2PG_RUN_BATCH")) e->batch_rounds = std::atoi(f);
-  if (const char* f = std::getenv("P2PG_DECAY_PRED")) e->decay_pred = std::strcmp(f, "0") != 0;
+  if (const char* f = std::getenv("P2PG_DECAY_PRED")) e->rules.decay_pred = std::strcmp(f, "0") != 0;
   if (const char* f = std::getenv("P2PG_PARTIAL_F")) e->partial_f = std::strcmp(f, "0") != 0;
   if (const char* f = std::getenv("P2PG_SEEN_SPARE")) e->seen_spare_on = std::strcmp(f, "0") != 0;
   if (const char* m = std::getenv("P2PG_GOSSIP_PUSH"))
-    e->push_mode = !std::strcmp(m, "atomic") ? 1 : (!std::strcmp(m, "store") ? 2 : 0);
+    e->rules.push_mode = !std::strcmp(m, "atomic") ? 1 : (!std::strcmp(m, "store") ? 2 : 0);
   HIPCHK(e, hipSetDevice(cfg->device));
   HIPCHK(e, hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
   e->stream = e->own_stream;
@@ -911,8 +852,8 @@ int upload_graph(p2pg_engine* e, int64_t V, const int64_t* rowptr, const int32_t
   free_topology(e);
   e->V = V;
   e->nnz = nnz;
-  e->v_conn = 0;
-  for (int64_t v = 0; v < V; ++v) e->v_conn += rowptr[v + 1] > rowptr[v];
+  e->rules.v_conn = 0;
+  for (int64_t v = 0; v < V; ++v) e->rules.v_conn += rowptr[v + 1] > rowptr[v];
   if (!rev.empty()) {
     HIPCHK(e, hipMalloc((void**)&e->d_rev, sizeof(uint32_t) * rev.size()));
     HIPCHK(e, hipMemcpy(e->d_rev, rev.data(), sizeof(uint32_t) * rev.size(), hipMemcpyHostToDevice));
@@ -1188,21 +1129,18 @@ bool policy_muted(const p2pg_engine* e, int64_t v, int32_t m, int32_t r) {
 }
 
 // The sends of the pending expiry or policy round become final: its expired and its muted frontier
-// bits are cleared (relay_expire.hip, relay_policy.hip; a round may have both), then the rest as
-// for an expiry round.  A pure policy round's held-back gossip push takes the form the round chose
-// from its own counters (pol_push_e): row atomics as below, or edge-mask stores into E that the
-// next round pulls.  A round that is also an expiry round keeps the row atomics.
-//
-// The sends of the pending expiry round become final: its expired frontier bits are cleared
-// (from here on p2pg_get_new_deliveries refuses that round), then -- push -- a gossip round's
-// held-back pushes leave as row atomics into the planes the next round's update consumes (no
-// push is made twice, no plane zeroed), and a churn run with P2PG_FLAG_RECEIVED counts the
-// round's lost sends, which it could not before the clearing.  Called at the top of the next
-// round, before the peer counters take the round in, and by the boundary calls that read or
-// change the round's sends; drop_relays and update_edges redo the gossip pushes themselves
-// (push = false).
-// Returns a P2PG code.  The passes are timed with their classes: k_expire with the origination
-// class 0 (like k_originate, a pass over the schedule's messages), the push with class 2.
+// bits are cleared (relay_expire.hip, relay_policy.hip; a round may have both; from here on
+// p2pg_get_new_deliveries refuses that round), then -- push -- a gossip round's held-back push
+// leaves in the form its plan resolved to at the round's end (held_push_e): row atomics into the
+// planes the next round's update consumes (an expiry round's always), or edge-mask stores into E
+// that the next round pulls.  No push is made twice, no plane zeroed.  A churn run with
+// P2PG_FLAG_RECEIVED then counts the round's lost sends, which it could not before the clearing.
+// Called at the top of the next round, before the peer counters take the round in, and by the
+// boundary calls that read or change the round's sends; drop_relays and update_edges redo the
+// gossip pushes themselves (push = false).
+// Returns a P2PG code.  The passes are timed with their classes: k_expire and k_policy with the
+// origination class 0 (like k_originate, a pass over the schedule's messages), the push with
+// class 6 or 2.
 int finalize_expiry(p2pg_engine* e, bool push) {
   if (e->exp_pending < 0 && e->pol_pending < 0) return P2PG_OK;
   const int32_t r = std::max(e->exp_pending, e->pol_pending);  // (both are the last round)
@@ -1228,8 +1166,8 @@ int finalize_expiry(p2pg_engine* e, bool push) {
   // the bits are gone (stream order): the round is final whatever happens below
   e->exp_pending = e->pol_pending = -1;
   e->exp_final = r;
-  if (push && e->cfg.mode == P2PG_MODE_GOSSIP && e->last_new > 0) {
-    if (xi < 0 && e->pol_push_e) {
+  if (push && e->cfg.mode == P2PG_MODE_GOSSIP && e->hist.last_new > 0) {
+    if (e->held_push_e) {
       // a policy round that chose the dense form from its own counters: edge-mask stores into
       // E[r&1], which the next round pulls (last_push_e stands since the round's end)
       rc = timed(e, 6, [&] {
@@ -1240,7 +1178,7 @@ int finalize_expiry(p2pg_engine* e, bool push) {
       // The list is sized by the round's nonzero frontier words before the clearing (prev_aw), which
       // bounds the words left after it: this push cannot outgrow its list, so its count is not read
       // back (check_scatter_list would cost the boundary a host synchronisation).
-      rc = timed(e, 2, [&] { return launch_scatter_atomic(e, g, p, std::max<uint64_t>(e->prev_aw, 1)); });
+      rc = timed(e, 2, [&] { return launch_scatter_atomic(e, g, p, std::max<uint64_t>(e->hist.prev_aw, 1)); });
       e->wlist_check = false;
     }
     e->stats_clear = true;  // the push counted into the round counters
@@ -1536,16 +1474,11 @@ int p2pg_reset(p2pg_engine* e) {
   e->auto_round = -1;
   e->frontier_kept = true;
   e->frontier_kept_prev = true;
-  e->last_push_e = false;
+  e->hist = rp::RoundHistory{};
   e->consume_next = false;
   e->total_relays = 0;
   e->sent_last = e->lost_last = 0;
   free_arr(e);
-  e->prev_aw = e->prev_av = 0;
-  e->last_new = 0;
-  e->prev2_aw = e->prev2_av = e->prev2_new = 0;
-  e->prev_sw = 0;
-  e->saw_dense = false;
   // (a previous run's unresolved launch timings belong to it, not to the next one)
   e->ev_cls.clear();
   for (int i = 0; i < P2PG_KCLASS_N; ++i) {
@@ -1563,7 +1496,41 @@ namespace {
 // Vertex-partitioned ranks with ghosts, rounds r >= 1 of the flood pull or the gossip update.
 bool split_round(const p2pg_engine* e) {
   return e->d_border && e->round > 0 && !e->consume_next &&
-         (e->cfg.mode == P2PG_MODE_FLOOD || !e->last_push_e);
+         (e->cfg.mode == P2PG_MODE_FLOOD || !e->hist.last_push_e);
+}
+
+// The end of round e->round with counters tot (p2pg_step, and every reported round of a decay
+// batch): fills out, rolls the schedule's history, takes the round's sends and frontier state in.
+// pushed_e: its gossip pushes went (or, held back, will go) to E; rows_whole: its frontier rows
+// were stored whole; lost: its counted lost sends.  Returns whether the run goes on: receipts in
+// flight, or a scheduled start at or after the next round.
+bool close_round(p2pg_engine* e, const uint64_t* tot, int32_t push_form, bool pushed_e, bool rows_whole,
+                 uint64_t lost, p2pg_round_stats* out) {
+  const bool active = tot[ST_NEW] != 0 || start_ahead(e, e->round + 1);
+  if (out) {
+    out->round = e->round;
+    out->active = active ? 1 : 0;
+    out->new_deliveries = tot[ST_NEW];
+    out->relays = tot[ST_RELAYS];
+    out->active_vertices = tot[ST_ACTIVE_V];
+    out->active_words = tot[ST_ACTIVE_W];
+    out->wedges = tot[ST_WEDGES];
+    out->deg_active = tot[ST_DEG_ACT];
+    out->scatter_words = tot[ST_SCATTER];
+    out->touched_words = tot[ST_AUX];
+    out->push_form = push_form;
+    out->received_exact = received_exact(e) ? 1 : 0;
+    out->received = e->round == 0 ? 0 : e->sent_last - e->lost_last;
+  }
+  rp::advance(e->hist, {tot[ST_NEW], tot[ST_ACTIVE_V], tot[ST_ACTIVE_W], tot[ST_SCATTER]}, pushed_e);
+  e->sent_last = tot[ST_RELAYS];
+  e->lost_last = lost;
+  e->total_relays += tot[ST_RELAYS];
+  e->frontier_kept_prev = e->frontier_kept;
+  e->frontier_kept = rows_whole || tot[ST_NEW] == 0;
+  e->round += 1;
+  if (!active && !(e->cfg.flags & P2PG_FLAG_NO_AUTOSTOP)) e->done = true;
+  return active;
 }
 
 }  // namespace
@@ -1633,75 +1600,70 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   }
   e->begun = false;
   const bool gossip = e->cfg.mode == P2PG_MODE_GOSSIP;
-  bool fused_round = false, up_round = false;
-  // A round with originations (start rounds > 0): they are injected into the frontier rows after
-  // the receive pass and before the pushes, so a gossip round takes the unfused schedule -- its
-  // receive pass, k_originate, then the separate push -- with whole frontier rows (a partial row
-  // cannot be ORed into) and its own counters read before the push (the last round's pushed masks
-  // do not bound words nobody pushed).  The rounds around it keep every form they have.
+  // What this round is (round_plan.h).  Its originations (start rounds > 0) are injected into the
+  // frontier rows after the receive pass and before the pushes.  Hop limits that expire in it
+  // (p2pg_set_ttl) and a relay policy (p2pg_set_relay_policy: every round after round 0, any of its
+  // first receipts may be muted) correct its counters below, and its sends -- a gossip round's
+  // push -- wait until they are final (finalize_expiry).
   const p2pg_engine::SchedRound* const orig = sched_round(e, e->round);
-  // A round in which hop limits expire (p2pg_set_ttl) is treated alike: the unfused schedule with
-  // whole frontier rows, which the correction pass and the boundary's clearing read and write
-  // (relay_expire.hip); its gossip push is held back until its sends are final (finalize_expiry).
   const int64_t xi = expiry_index(e, e->round);
-  // With a relay policy (p2pg_set_relay_policy) every round after round 0 is: any of its first
-  // receipts may be muted (relay_policy.hip), and its gossip push is held back in the same way --
-  // in the form chosen below from the round's own counters.
   const bool pol = e->pol_on && e->round > 0;
-  const bool plain = orig != nullptr || xi >= 0 || pol;
-  // the update / pull-only pass of this round (fused and update+push rounds set their own)
-  if (gossip && !plain && partial_frontier(e, e->skip_frontier)) p.store_f = 2;
-  uint64_t host_new = 0, host_relays = 0, host_av = 0, host_aw = 0, host_wedge = 0, host_degact = 0;
-  if (e->round == 0) {
-    if ((rc = timed(e, 0, [&] { return launch_zero_rows(s.F[0], e->W, e->d_src, e->M, e->stream); }))) return rc;
-    if (s.AW[0])
-      if ((rc = timed(e, 0, [&] { return launch_zero_rows(s.AW[0], 1, e->d_src, e->M, e->stream); }))) return rc;
-    if ((rc = timed(e, 0, [&] { return launch_seed(s, e->d_src, e->M, e->stream); }))) return rc;
-    // origination stats from the host copy of the sources (computed once per sources and graph)
+  const rp::RoundCaps caps = round_caps(e);
+  rp::RoundFacts facts;
+  facts.round = e->round;
+  facts.consume_next = e->consume_next;
+  facts.split = p.phase >= 0;
+  facts.origination = orig != nullptr;
+  facts.expiry = xi >= 0;
+  facts.policy = pol;
+  facts.skip_frontier = e->skip_frontier;
+  const rp::RoundPlan plan = rp::plan_round(e->hist, e->rules, caps, facts);
+  p.store_f = plan.store_f;
+  uint64_t tot[STAT_N] = {0};
+  // round 0's counters are the host's: origination stats from the host copy of the sources
+  // (computed once per sources and graph)
+  auto host_stats = [&] {
     const SeedStats& ss = seed_stats(e);
-    host_new = ss.nw;
-    host_relays = ss.relays;
-    host_av = ss.av;
-    host_aw = ss.aw;
-    host_wedge = ss.wedge;
-    host_degact = ss.degact;
-  } else if (e->consume_next) {
-    // arrivals materialized into row pushes (topology update / restored snapshot)
-    if ((rc = timed(e, 4, [&] { return launch_gossip_update(g, s, p, e->stream); }))) return rc;
-    e->consume_next = false;
-  } else if (!gossip) {
-    if ((rc = timed(e, 1, [&] { return launch_flood_pull(g, s, p, e->hp, e->stream); }))) return rc;
-  } else if (e->last_push_e) {
-    // previous round stored per-edge masks: gather them (pull, no atomics).  If this round is
-    // predicted dense as well (the previous round's word density; the prediction only picks
-    // the push form, never the result), the same pass also pushes this round's receipts.
-    const bool dense_pred = e->push_mode == 2 || (e->push_mode == 0 && still_dense(e));
-    const bool part = e->d_gid != nullptr;  // (a rank gets here only if part_dense)
-    fused_round = !plain && (!part || part_dense(e)) && dense_pred && gossip_fused_supported(s);
-    if (fused_round) {
-      // a frontier nobody observes is not stored: inside p2pg_run (not its last allowed
-      // round), without hop/parent records
-      p.store_f = (e->skip_frontier && !s.hop) ? 0 : 1;
-      if ((rc = timed(e, 7, [&] { return launch_fused_round(e, g, p); }))) return rc;
-    } else {
+    tot[ST_NEW] = ss.nw;
+    tot[ST_RELAYS] = ss.relays;
+    tot[ST_ACTIVE_V] = ss.av;
+    tot[ST_ACTIVE_W] = ss.aw;
+    tot[ST_WEDGES] = ss.wedge;
+    tot[ST_DEG_ACT] = ss.degact;
+  };
+  switch (plan.receive) {
+    case rp::Receive::Seed:
+      if ((rc = timed(e, 0, [&] { return launch_zero_rows(s.F[0], e->W, e->d_src, e->M, e->stream); }))) return rc;
+      if (s.AW[0])
+        if ((rc = timed(e, 0, [&] { return launch_zero_rows(s.AW[0], 1, e->d_src, e->M, e->stream); }))) return rc;
+      if ((rc = timed(e, 0, [&] { return launch_seed(s, e->d_src, e->M, e->stream); }))) return rc;
+      host_stats();
+      break;
+    case rp::Receive::Consume:  // arrivals materialized into row pushes (topology update / snapshot)
+    case rp::Receive::Update:
+      if ((rc = timed(e, 4, [&] { return launch_gossip_update(g, s, p, e->stream); }))) return rc;
+      e->consume_next = false;
+      break;
+    case rp::Receive::FloodPull:
+      if ((rc = timed(e, 1, [&] { return launch_flood_pull(g, s, p, e->hp, e->stream); }))) return rc;
+      break;
+    case rp::Receive::GossipPull:  // (a partitioned rank gets here only if part_dense)
       if ((rc = timed(e, 5, [&] {
              hipError_t r = launch_gossip_pull(g, s, p, e->hp, e->stream);
-             return r != hipSuccess || !part ? r : launch_clear_arrivals(s, p.round, e->V, e->stream);
+             return r != hipSuccess || !e->d_gid ? r : launch_clear_arrivals(s, p.round, e->V, e->stream);
            })))
         return rc;
-    }
-  } else if (!plain && update_push_round(e, p)) {
-    // the first dense round after a sparse one: update and E pushes in one pass (timed with the
-    // store pushes); the frontier rows follow the fused rounds' rule
-    up_round = true;
-    p.store_f = (e->skip_frontier && !s.hop) ? 0 : 1;
-    if ((rc = timed(e, 6, [&] {
-           return launch_gossip_update_push(g, s, p, e->d_hub_big, e->n_hub_big, e->d_wide_big,
-                                            e->n_wide_big, e->stream);
-         })))
-      return rc;
-  } else {
-    if ((rc = timed(e, 4, [&] { return launch_gossip_update(g, s, p, e->stream); }))) return rc;
+      break;
+    case rp::Receive::Fused:
+      if ((rc = timed(e, 7, [&] { return launch_fused_round(e, g, p); }))) return rc;
+      break;
+    case rp::Receive::UpdatePush:  // (timed with the store pushes)
+      if ((rc = timed(e, 6, [&] {
+             return launch_gossip_update_push(g, s, p, e->d_hub_big, e->n_hub_big, e->d_wide_big,
+                                              e->n_wide_big, e->stream);
+           })))
+        return rc;
+      break;
   }
   if (orig)  // Node.send_to_nodes at the origins of this round (node.py:106-112)
     if ((rc = timed(e, 0, [&] {
@@ -1714,7 +1676,6 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
            return launch_record(graph_for_arrivals(e, e->round), s, p, e->stream);
          })))
       return rc;
-  uint64_t tot[STAT_N] = {0};
   auto read_stats = [&]() -> int {
     HIPCHK(e, hipMemcpyAsync(e->h_stats, s.stats, STAT_BYTES, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, round_sync(e));
@@ -1724,69 +1685,18 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     for (int sh = 0; sh < STAT_SHARDS; ++sh)
       for (int i = 0; i < STAT_N; ++i)
         tot[i] += e->h_stats[sh * STAT_N + i] - e->stats_base[sh * STAT_N + i];
-    if (e->round == 0) {
-      tot[ST_NEW] = host_new;
-      tot[ST_RELAYS] = host_relays;
-      tot[ST_ACTIVE_V] = host_av;
-      tot[ST_ACTIVE_W] = host_aw;
-      tot[ST_WEDGES] = host_wedge;
-      tot[ST_DEG_ACT] = host_degact;
-    }
+    if (e->round == 0) host_stats();
     return P2PG_OK;
   };
-  if (gossip && (fused_round || up_round)) {
-    e->last_push_e = true;  // the fused launches pushed every source of this round
-  } else if (gossip && (xi >= 0 || pol)) {
-    // an expiry round: its pushes wait until the expired frontier bits are cleared, when its sends
-    // become final (finalize_expiry: row atomics into the planes the next round's update consumes).
-    // A policy round's wait alike; its form is chosen at the round's end (below)
-    e->last_push_e = false;
-  } else if (gossip) {
-    // push form for this round's sends: row atomics when the frontier is sparse, whole-row
-    // edge-mask stores (+ pull next round) when most words of the active rows are set
-    bool use_e = false, have_tot = false;
-    // the counters of this round are needed before its push only to choose the form (unless
-    // that choice is clear already) and to size the sparse push's (peer, word) list (else
-    // bounded by the last round's pushed masks).  Not on a vertex-partitioned rank: rows other
-    // ranks pushed arrive by the exchange, so this rank's own pushed masks bound nothing
-    const bool blind = e->round > 0 && e->push_mode != 2 && !e->d_gid && !plain && clearly_sparse(e) &&
-                       e->prev_sw > 0;
-    // (partitioned ranks: E for their local connections when part_dense, ghost rows travel)
-    if (s.E[0] && (!e->d_gid || part_dense(e))) {
-      if (e->push_mode == 2) {
-        use_e = true;
-      } else if (e->push_mode == 0 && !blind) {
-        if (e->round == 0) {  // round 0's counters are the host's (seed_stats): no read-back
-          tot[ST_ACTIVE_W] = host_aw;
-          tot[ST_ACTIVE_V] = host_av;
-        } else if ((rc = read_stats())) {
-          return rc;
-        }
-        have_tot = true;
-        use_e = (double)tot[ST_ACTIVE_W] >=
-                e->e_thresh * (double)tot[ST_ACTIVE_V] * (double)e->W && tot[ST_ACTIVE_V] > 0 &&
-                (double)tot[ST_ACTIVE_V] >= e->v_thresh * (double)e->v_conn;
-      }
-    }
-    // the lane-parallel sparse push sizes its (peer, word) list by the frontier's word count
-    if (!use_e && !have_tot && !blind && sparse_scatter_on(e)) {
-      if (e->round == 0) {
-        tot[ST_ACTIVE_W] = host_aw;
-        tot[ST_ACTIVE_V] = host_av;
-      } else if ((rc = read_stats())) {
-        return rc;
-      }
-      have_tot = true;
-    }
-    // decay phase (fewer first receipts than the round before): most pushes are duplicates,
-    // so the sparse push drops seen bits before its atomics (RoundParams::dedup_push).  The
-    // phase is "after the dense rounds" (saw_dense), a fact every schedule agrees on -- a
-    // batched decay round, a blind push and a round that read its counters first must filter
-    // alike, because the filter decides which fully-seen masks are still pushed, i.e. the
-    // touched-words counter of the next round (results never depend on it)
-    if (!use_e && sparse_scatter_on(e))
-      p.dedup_push = e->push_dedup == 1 || (e->push_dedup < 0 && e->saw_dense);
-    const uint64_t list_words = have_tot ? tot[ST_ACTIVE_W] : e->prev_sw;
+  // did this round's pushes go to E?  The fused and update+push launches pushed every source
+  bool pushed_e = plan.push == rp::Push::Made;
+  if (gossip && !pushed_e && !plan.held) {
+    // the push the plan names, after the round's own counters where it asks for them
+    if (plan.mid_read && (rc = read_stats())) return rc;
+    const bool use_e =
+        rp::resolve_push(plan, e->rules, tot[ST_ACTIVE_W], tot[ST_ACTIVE_V]) == rp::Push::Edge;
+    if (!use_e && caps.sparse_scatter) p.dedup_push = rp::push_dedup(e->hist, e->rules);
+    const uint64_t list_words = plan.list == rp::PushList::Counters ? tot[ST_ACTIVE_W] : e->hist.prev_sw;
     if ((rc = timed(e, use_e ? 6 : 2, [&] {
            return use_e ? launch_gossip_scatter(g, s, p, e->d_hub, e->n_hub, true, e->stream,
                                                 e->d_hub_big, e->n_hub_big, e->d_wide_big,
@@ -1794,7 +1704,7 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
                         : launch_scatter_atomic(e, g, p, list_words);
          })))
       return rc;
-    e->last_push_e = use_e;
+    pushed_e = use_e;
   }
   if (e->auto_buf && e->d_seg_cnt) {
     // partitioned ranks: pack this round's live boundary rows now, so the one synchronisation
@@ -1839,10 +1749,9 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
          })))
       return rc;
     e->pol_pending = e->round;
-    e->pol_push_e = false;
   }
   // (an expiry or policy round's lost sends are counted once its bits are cleared: finalize_expiry)
-  const bool cnt_lost = count_lost_on(e) && xi < 0 && !pol;
+  const bool cnt_lost = count_lost_on(e) && !plan.held;
   if (cnt_lost) {  // this round's lost sends: the next round's arrivals are its sends minus them
     hipError_t x = enqueue_lost_count(e, g, graph_for_arrivals(e, e->round), e->round);
     if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("step (lost sends): ") + hipGetErrorString(x));
@@ -1850,20 +1759,16 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   if ((rc = read_stats())) return rc;
   std::memcpy(e->stats_base, e->h_stats, sizeof(e->stats_base));  // the next round counts from here
   if ((rc = check_scatter_list(e, e->h_stats[STAT_COUNT]))) return rc;
-  if (gossip && pol && xi < 0 && s.E[0]) {
-    // the form of this policy round's held-back push, by the rule of the rounds that push at once
-    // (P2PG_GOSSIP_PUSH; auto: the density of the round's own frontier, before the muting).  A
-    // dense round by row atomics only would run at the atomic units' rate
-    e->pol_push_e = e->push_mode == 2 ||
-                    (e->push_mode == 0 && tot[ST_ACTIVE_V] > 0 &&
-                     (double)tot[ST_ACTIVE_W] >= e->e_thresh * (double)tot[ST_ACTIVE_V] * (double)e->W &&
-                     (double)tot[ST_ACTIVE_V] >= e->v_thresh * (double)e->v_conn);
-    e->last_push_e = e->pol_push_e;  // (the next round pulls E; push_form reports it)
+  if (plan.held) {
+    // the form of the held-back push, by the rule of the rounds that push at once (the density of
+    // the round's own frontier, before the muting); the next round pulls E, push_form reports it
+    e->held_push_e = rp::resolve_push(plan, e->rules, tot[ST_ACTIVE_W], tot[ST_ACTIVE_V]) == rp::Push::Edge;
+    pushed_e = e->held_push_e;
   }
   if (e->auto_round == e->round)  // the round's own pack landed with its counters
     for (int q = 0; q + 1 < (int)e->send_seg.size(); ++q) e->auto_cnt[q] = (int64_t)e->h_seg_cnt[q];
 #ifdef P2PG_PROF
-  if (fused_round && s.prof && std::getenv("P2PG_PROF_ROUNDS")) {
+  if (plan.receive == rp::Receive::Fused && s.prof && std::getenv("P2PG_PROF_ROUNDS")) {
     // development builds: per-round fused-kernel segment clocks (then reset)
     unsigned long long h[9];
     HIPCHK(e, hipMemcpy(h, s.prof, sizeof(h), hipMemcpyDeviceToHost));
@@ -1873,42 +1778,11 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     fprintf(stderr, "\n");
   }
 #endif
-  // in flight, or a scheduled start lies at or after the next round
-  const bool active = tot[ST_NEW] != 0 || start_ahead(e, e->round + 1);
-  e->frontier_kept_prev = e->frontier_kept;
-  e->frontier_kept = !(((fused_round || up_round) && !p.store_f) || p.store_f == 2) || tot[ST_NEW] == 0;
-  if (out) {
-    out->round = e->round;
-    out->active = active ? 1 : 0;
-    out->new_deliveries = tot[ST_NEW];
-    out->relays = tot[ST_RELAYS];
-    out->active_vertices = tot[ST_ACTIVE_V];
-    out->active_words = tot[ST_ACTIVE_W];
-    out->wedges = tot[ST_WEDGES];
-    out->deg_active = tot[ST_DEG_ACT];
-    out->scatter_words = tot[ST_SCATTER];
-    out->touched_words = tot[ST_AUX];
-    out->push_form = !gossip ? P2PG_PUSH_NONE
-                     : fused_round ? P2PG_PUSH_FUSED
-                     : up_round ? P2PG_PUSH_UPDATE_EDGE
-                     : e->last_push_e ? P2PG_PUSH_EDGE : P2PG_PUSH_ATOMIC;
-    out->received_exact = received_exact(e) ? 1 : 0;
-    out->received = e->round == 0 ? 0 : e->sent_last - e->lost_last;
-  }
-  e->sent_last = tot[ST_RELAYS];
-  e->lost_last = cnt_lost ? (uint64_t)e->h_cnt2[1] : 0;
-  e->total_relays += tot[ST_RELAYS];
-  e->prev2_aw = e->prev_aw;
-  e->prev2_av = e->prev_av;
-  e->prev2_new = e->last_new;
-  e->prev_aw = tot[ST_ACTIVE_W];
-  e->prev_av = tot[ST_ACTIVE_V];
-  e->last_new = tot[ST_NEW];
-  e->prev_sw = tot[ST_SCATTER];
-  if (e->last_push_e) e->saw_dense = true;
-  e->round += 1;
-  if (!active && !(e->cfg.flags & P2PG_FLAG_NO_AUTOSTOP)) e->done = true;
-  return active ? 1 : 0;
+  const int32_t form = !gossip ? P2PG_PUSH_NONE
+                       : plan.receive == rp::Receive::Fused ? P2PG_PUSH_FUSED
+                       : plan.receive == rp::Receive::UpdatePush ? P2PG_PUSH_UPDATE_EDGE
+                       : pushed_e ? P2PG_PUSH_EDGE : P2PG_PUSH_ATOMIC;
+  return close_round(e, tot, form, pushed_e, p.store_f == 1, cnt_lost ? (uint64_t)e->h_cnt2[1] : 0, out) ? 1 : 0;
 }
 
 int p2pg_step_end(p2pg_engine* e, p2pg_round_stats* out) { return p2pg_step(e, out); }
@@ -1929,19 +1803,18 @@ constexpr int BATCH_MAX = 8;
 
 static bool decay_batchable(const p2pg_engine* e) {
   const int br = e->batch_rounds < 0 ? BATCH_MAX : e->batch_rounds;
-  return br > 1 && e->have_state && !e->done && !e->begun && e->round > 0 && !frontier_needed(e) &&
-         e->cfg.mode == P2PG_MODE_GOSSIP && e->saw_dense && !e->last_push_e &&
-         e->last_new < e->prev2_new && e->prev_sw > 0 && !e->consume_next && e->arr_round < 0 &&
-         // every start in round 0: a batch's list is sized for one wave's decay (each round's
-         // frontier smaller than the last); with start rounds a younger wave may still be growing
-         // under the older ones' decay and outgrow it mid-batch, and an origination round reads its
-         // own counters before its push
-         e->last_start == 0 &&
-         // no hop limit expires from here on: an expiry round runs its own schedule (p2pg_step)
-         !expiry_ahead(e, e->round) &&
-         !e->d_gid && !(e->cfg.flags & P2PG_FLAG_NO_AUTOSTOP) && e->push_mode != 2 &&
-         e->auto_buf == nullptr && sparse_scatter_on(e) &&
-         e->last_new * 16 < (uint64_t)e->V;  // the tail: small rounds, where the syncs dominate
+  if (br <= 1 || !e->have_state || e->done || e->begun) return false;
+  rp::DecayFacts f;
+  f.round = e->round;
+  f.V = e->V;
+  f.consume_next = e->consume_next;
+  f.late_starts = e->last_start != 0;
+  f.expiry_ahead = expiry_ahead(e, e->round);
+  f.frontier_needed = frontier_needed(e);
+  f.autostop = !(e->cfg.flags & P2PG_FLAG_NO_AUTOSTOP);
+  f.auto_buf = e->auto_buf != nullptr;
+  f.arr_pending = e->arr_round >= 0;
+  return rp::decay_batchable(e->hist, e->rules, round_caps(e), f);
 }
 
 // n_left: rounds the p2pg_run call may still run (its last two keep their frontier rows whole).
@@ -1957,7 +1830,7 @@ static int run_decay_batch(p2pg_engine* e, int32_t R, p2pg_round_stats* out, int
   HIPCHK(e, hipMemsetAsync(e->d_bstats, 0, sizeof(unsigned long long) * SLOT * R, e->stream));
   // the list, sized once for the batch: the first round's bound, doubled for the others
   SparseBufs b;
-  hipError_t lr = sparse_bufs(e, 2 * (int64_t)e->prev_sw, b);
+  hipError_t lr = sparse_bufs(e, 2 * (int64_t)e->hist.prev_sw, b);
   if (lr != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("run (batch list): ") + hipGetErrorString(lr));
   const uint64_t words = (uint64_t)e->wlist_cap;  // no round of the batch grows the list
   unsigned long long* const stats0 = s.stats;
@@ -1968,14 +1841,14 @@ static int run_decay_batch(p2pg_engine* e, int32_t R, p2pg_round_stats* out, int
     s.stats = e->d_bstats + SLOT * i;
     RoundParams p = params(e);
     p.round = e->round + i;
-    if (partial_frontier(e, i + 2 < n_left)) p.store_f = 2;
+    if (i + 2 < n_left && partial_rows(e)) p.store_f = 2;
     partial[i] = p.store_f == 2;
     rc = timed(e, 4, [&] { return launch_gossip_update(g, s, p, e->stream); });
     if (rc == P2PG_OK && s.hop) rc = timed(e, 3, [&] { return launch_record(g, s, p, e->stream); });
-    p.dedup_push = e->push_dedup != 0;  // decay phase (saw_dense: the rule of p2pg_step)
+    p.dedup_push = rp::push_dedup(e->hist, e->rules);
     if (rc == P2PG_OK)
       rc = timed(e, 2, [&] {
-        return launch_scatter_atomic(e, g, p, std::min<uint64_t>(e->prev_sw, words));
+        return launch_scatter_atomic(e, g, p, std::min<uint64_t>(e->hist.prev_sw, words));
       });
   }
   s.stats = stats0;
@@ -1999,39 +1872,10 @@ static int run_decay_batch(p2pg_engine* e, int32_t R, p2pg_round_stats* out, int
     uint64_t tot[STAT_N] = {0};
     for (int sh = 0; sh < STAT_SHARDS; ++sh)
       for (int q = 0; q < STAT_N; ++q) tot[q] += h[sh * STAT_N + q];
-    const bool active = tot[ST_NEW] != 0;
-    p2pg_round_stats& o = out[i];
-    o.round = e->round;
-    o.active = active ? 1 : 0;
-    o.new_deliveries = tot[ST_NEW];
-    o.relays = tot[ST_RELAYS];
-    o.active_vertices = tot[ST_ACTIVE_V];
-    o.active_words = tot[ST_ACTIVE_W];
-    o.wedges = tot[ST_WEDGES];
-    o.deg_active = tot[ST_DEG_ACT];
-    o.scatter_words = tot[ST_SCATTER];
-    o.touched_words = tot[ST_AUX];
-    o.push_form = P2PG_PUSH_ATOMIC;
-    o.received_exact = received_exact(e) ? 1 : 0;
-    o.received = e->round == 0 ? 0 : e->sent_last - e->lost_last;
-    e->sent_last = tot[ST_RELAYS];
-    e->lost_last = 0;  // (no churn in a batched run)
-    e->total_relays += tot[ST_RELAYS];
-    e->frontier_kept_prev = e->frontier_kept;
-    e->frontier_kept = !(partial[i] && active);
-    e->prev2_aw = e->prev_aw;
-    e->prev2_av = e->prev_av;
-    e->prev2_new = e->last_new;
-    e->prev_aw = tot[ST_ACTIVE_W];
-    e->prev_av = tot[ST_ACTIVE_V];
-    e->last_new = tot[ST_NEW];
-    e->prev_sw = tot[ST_SCATTER];
-    e->round += 1;
+    // (no churn in a batched run: no lost sends)
+    const bool active = close_round(e, tot, P2PG_PUSH_ATOMIC, false, !partial[i], 0, &out[i]);
     *ran = i + 1;
-    if (!active) {
-      e->done = true;  // (rounds enqueued after this one saw an empty frontier)
-      break;
-    }
+    if (!active) break;  // the run is done (rounds enqueued after this one saw an empty frontier)
   }
   return P2PG_OK;
 }
@@ -2079,7 +1923,7 @@ int p2pg_get_new_deliveries(p2pg_engine* e, int64_t cap, int32_t* peer, int32_t*
     return fail(e, P2PG_ERR_ARG, "get_new_deliveries: bad arguments");
   if (!e->have_state || e->round == 0)
     return fail(e, P2PG_ERR_STATE, "get_new_deliveries: no round has run");
-  if (e->last_new == 0) {  // a round without receipts has no deliveries (and needs no parents)
+  if (e->hist.last_new == 0) {  // a round without receipts has no deliveries (and needs no parents)
     *n_out = 0;
     return P2PG_OK;
   }
@@ -2149,7 +1993,7 @@ static int sends_state(p2pg_engine* e, const char* what) {
   if (e->begun) return fail(e, P2PG_ERR_STATE, w + ": a round has begun (step_begin)");
   if (e->arr_round >= 0 && e->arr_round == e->round)
     return fail(e, P2PG_ERR_STATE, w + ": the connections changed since the round (call it before p2pg_update_edges)");
-  if (e->last_new == 0) return P2PG_OK;
+  if (e->hist.last_new == 0) return P2PG_OK;
   if (!e->frontier_kept) return fail(e, P2PG_ERR_STATE, w + ": the last round's frontier was not kept");
   if (e->cfg.mode == P2PG_MODE_FLOOD && e->round > 1 && !e->frontier_kept_prev)
     return fail(e, P2PG_ERR_STATE, w + ": the senders' parents need the frontier of the round before, "
@@ -2163,7 +2007,7 @@ int p2pg_get_sends(p2pg_engine* e, int64_t cap, int32_t* sender, int32_t* receiv
     return fail(e, P2PG_ERR_ARG, "get_sends: bad arguments");
   int rc = sends_state(e, "get_sends");
   if (rc) return rc;
-  if (e->last_new == 0) {
+  if (e->hist.last_new == 0) {
     *n_out = 0;
     return P2PG_OK;
   }
@@ -2303,7 +2147,7 @@ int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32
     if (lr == hipSuccess) lr = hipMemsetAsync(s.T[nx], 0, e->bm_bytes, e->stream);
     RoundParams p = params(e);
     p.round = r;
-    if (lr == hipSuccess) lr = launch_scatter_atomic(e, graph(e), p, std::max<uint64_t>(e->prev_aw, 1));
+    if (lr == hipSuccess) lr = launch_scatter_atomic(e, graph(e), p, std::max<uint64_t>(e->hist.prev_aw, 1));
   }
   if (lr == hipSuccess && count_lost_on(e))
     lr = enqueue_lost_count(e, graph(e), graph_for_arrivals(e, r), r);
@@ -2316,7 +2160,7 @@ int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32
   if (gossip) {
     if (e->wlist_check && (rc = check_scatter_list(e, listed))) return rc;
     e->consume_next = true;
-    e->last_push_e = false;
+    e->hist.last_push_e = false;
     e->stats_clear = true;  // the re-push counted into the round counters
   }
   if (count_lost_on(e)) e->lost_last = (uint64_t)e->h_cnt2[1];
@@ -2787,7 +2631,7 @@ int p2pg_update_edges(p2pg_engine* e, int64_t n_add, const int32_t* add, int64_t
       HIPCHK(e, hipMemsetAsync(s.next[nx], 0, e->plane_bytes, e->stream));
       HIPCHK(e, hipMemsetAsync(s.T[nx], 0, e->bm_bytes, e->stream));
       p.round = e->round - 1;
-      lr = launch_scatter_atomic(e, gold, p, e->prev_aw);
+      lr = launch_scatter_atomic(e, gold, p, e->hist.prev_aw);
       if (lr != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("update_edges: ") + hipGetErrorString(lr));
     }
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -2797,7 +2641,7 @@ int p2pg_update_edges(p2pg_engine* e, int64_t n_add, const int32_t* add, int64_t
       if (int rc2 = check_scatter_list(e, listed)) return rc2;
     }
     e->consume_next = true;
-    e->last_push_e = false;
+    e->hist.last_push_e = false;
     e->stats_clear = true;  // the re-push above counted into the round counters
     // keep the old rows for the parents of the receiving round (record / deliveries)
     e->d_rowptr_arr = e->d_rowptr;
@@ -2914,18 +2758,18 @@ int p2pg_snapshot(p2pg_engine* e, void* buf, int64_t cap) {
     return fail(e, P2PG_ERR_STATE, "snapshot: take it before a topology update or after the next round");
   if (!e->frontier_kept)
     return fail(e, P2PG_ERR_STATE, "snapshot: the last round's frontier was not kept");
-  if (e->d_gid && e->cfg.mode == P2PG_MODE_GOSSIP && e->last_push_e && e->round > 0 && !e->done)
+  if (e->d_gid && e->cfg.mode == P2PG_MODE_GOSSIP && e->hist.last_push_e && e->round > 0 && !e->done)
     return fail(e, P2PG_ERR_STATE,
                 "snapshot: a partitioned rank holds this round's pushes per connection; take it "
                 "after a sparse round");
   HIPCHK(e, hipSetDevice(e->cfg.device));
   DevState& s = e->st;
-  if (e->cfg.mode == P2PG_MODE_GOSSIP && e->last_push_e && e->round > 0 && !e->done) {
+  if (e->cfg.mode == P2PG_MODE_GOSSIP && e->hist.last_push_e && e->round > 0 && !e->done) {
     // pushes held per connection (E) -> row pushes, so the state does not depend on slots
     RoundParams p = params(e);
     hipError_t lr = launch_materialize(graph(e), s, p, false, e->stream);
     if (lr != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("snapshot: ") + hipGetErrorString(lr));
-    e->last_push_e = false;
+    e->hist.last_push_e = false;
     e->stats_clear = true;
   }
   HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -2952,9 +2796,9 @@ int p2pg_snapshot(p2pg_engine* e, void* buf, int64_t cap) {
   h.graph_hash = graph_hash(e);
   h.src_hash = fnv1a(0xCBF29CE484222325ull, e->h_src.data(), e->h_src.size() * sizeof(int32_t));
   h.total_relays = e->total_relays;
-  h.prev_aw = e->prev_aw;
-  h.prev_av = e->prev_av;
-  h.last_new = e->last_new;
+  h.prev_aw = e->hist.prev_aw;
+  h.prev_av = e->hist.prev_av;
+  h.last_new = e->hist.last_new;
   h.sent_last = e->sent_last;
   h.lost_last = e->lost_last;
   char* out = (char*)buf;
@@ -3020,18 +2864,17 @@ int p2pg_restore(p2pg_engine* e, const void* buf, int64_t size) {
   e->round = h.round;
   e->done = h.done != 0;
   e->consume_next = h.consume_next != 0;
-  e->last_push_e = false;
   e->total_relays = h.total_relays;
-  e->prev_aw = h.prev_aw;
-  e->prev_av = h.prev_av;
-  e->last_new = h.last_new;
+  e->hist.prev_aw = h.prev_aw;
+  e->hist.prev_av = h.prev_av;
+  e->hist.last_new = h.last_new;
   e->sent_last = h.sent_last;
   e->lost_last = h.lost_last;
   // the snapshot holds the last round's frontier, not the one before it, so that round's
   // delivery parents cannot be found (round 0's are -1): deliveries refuse it, as documented
   e->frontier_kept = true;
   e->frontier_kept_prev = h.round <= 1;
-  e->prev2_aw = e->prev2_av = e->prev2_new = 0;  // no growth history: no update+push prediction
+  // (the reset above left no growth history: no update+push prediction, no dense phase seen)
   const char* in = (const char*)buf;
   size_t off = sizeof(h);
   rc = for_planes(e, with_next, [&](void* dev, size_t n) -> int {
