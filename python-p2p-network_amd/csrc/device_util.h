@@ -208,6 +208,67 @@ __device__ __forceinline__ void list_bits(uint16_t* lst, uint32_t dummy, uint64_
   }
 }
 
+// A/B switch (profiles/pick_path): 0 = every row through list_bits' windowed loop.
+#ifndef P2PG_LIST_WHOLE
+#define P2PG_LIST_WHOLE 1
+#endif
+
+// Index of the lowest set bit; all ones for x = 0 (v_ffbl_b32: defined there, unlike ctz).
+__device__ __forceinline__ uint32_t ffs_any(uint32_t x) {
+  uint32_t r;
+  asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(x));
+  return r;
+}
+
+// list_bits for a list that fits one window (total <= cap: wave-uniform, nearly every row), so no
+// position needs a `< cap` test.  Per half and trip: x - 1 and its carry (x != 0: this half still
+// has a bit) from one add, the write position as a pointer advancing one entry, the find-first-set
+// defined for zero (an exhausted half's entry goes to the dummy, its value is never read).  The
+// loop ends when no lane has a bit left -- the carries it computes anyway, ORed on the scalar
+// side -- so no max-reduce of the popcounts up front.
+__device__ __forceinline__ void list_bits_whole(uint16_t* lst, uint32_t dummy, uint64_t f,
+                                                uint32_t tag, uint32_t li0) {
+  uint32_t lo = (uint32_t)f, hi = (uint32_t)(f >> 32);
+  uint16_t* al = lst + li0;
+  uint16_t* ah = al + __popc(lo);
+  uint16_t* const dm = lst + dummy;
+  uint32_t th = tag | 32u;
+  asm("" : "+v"(th));  // kept whole in a register: else (tag | bit) | 32, two ORs per trip
+  uint32_t ml, mh;  // lo - 1, hi - 1
+  bool cl = __builtin_add_overflow(lo, ~0u, &ml), ch = __builtin_add_overflow(hi, ~0u, &mh);
+  while (__builtin_amdgcn_ballot_w64(cl || ch)) {
+    *(cl ? al : dm) = (uint16_t)(tag | ffs_any(lo));
+    *(ch ? ah : dm) = (uint16_t)(th | ffs_any(hi));
+    lo &= ml;
+    hi &= mh;
+    ++al;
+    ++ah;
+    cl = __builtin_add_overflow(lo, ~0u, &ml);
+    ch = __builtin_add_overflow(hi, ~0u, &mh);
+  }
+}
+
+// The first list entry of lane `lane` in a pick loop over entries [0, n), n >= 1, nbat =
+// ceil(n / 64) consecutive entries per lane (lane l: l*nbat ...).  A lane whose share runs past n
+// does not idle: the table ORs are idempotent and the picks a pure function of (round, peer,
+// message), so it evaluates valid entries a second time and ORs the same bits again -- no `ok`
+// mask, no guard against stale entries.  The run of every lane lies inside [0, n):
+//   n >= 64: the lane that straddles n starts at n - nbat instead (its run still covers its own
+//            entries); a lane wholly past n starts at l*nbat - n < 63 (unsigned: the smallest
+//            of the three);
+//   n <  64: lane l >= n takes entry l & (2^floor(log2 n) - 1).
+// The duplicates are spread over the list on purpose: lanes that evaluate the same entry in the
+// same trip issue same-address LDS atomics, which serialise.
+__device__ __forceinline__ uint32_t pick_first(uint32_t lane, uint32_t n, uint32_t nbat) {
+  const uint32_t i0 = lane * nbat;
+  if (n >= 64u) {
+    const uint32_t a = i0 < n - nbat ? i0 : n - nbat, b = i0 - n;
+    return a < b ? a : b;
+  }
+  const uint32_t pm = (1u << (31 - __builtin_clz(n | 1u))) - 1u;
+  return lane < n ? lane : lane & pm;
+}
+
 // Orders this wave's LDS writes before its later LDS reads by other lanes.
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");

@@ -1106,6 +1106,11 @@ __global__ __launch_bounds__(256) void k_materialize(DevGraph g, DevState st, Ro
 #define PROF_PASS
 #endif
 
+// A/B switch (profiles/pick_path): 0 = idle pick lanes evaluate a stale entry under an empty mask.
+#ifndef P2PG_PICK_DUP
+#define P2PG_PICK_DUP 1
+#endif
+
 // LDS of one scatter wave: a GCHUNK x 64-word mask table (two 32-bit halves per word, so
 // 32-bit LDS atomics) and the compacted list of active (word, bit) entries.
 // Half-major rows: connection j's row is [half][word], so the
@@ -1208,6 +1213,18 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
     // their table atomics hit different LDS banks.  The next batch's entry is read before this
     // batch's Philox (hides the LDS trip).
     const uint32_t nbat = (n + 63) >> 6;
+#if P2PG_PICK_DUP
+    // Uniform trip count: a lane past its share evaluates valid entries a second time
+    // (pick_first), so the loop has no per-lane exit bookkeeping, no mask select and no guard
+    // against stale entries; the entry pointer advances by one per trip.  q + nbat <= lst + n.
+    const uint16_t* q = L.lst + pick_first((uint32_t)lane, n, nbat);
+    uint32_t en = *q;
+    for (uint32_t b = 0; b < nbat; ++b) {
+      const uint32_t e = en;
+      en = *++q;
+      one(check_v, e, true);
+    }
+#else
     const uint32_t i0 = (uint32_t)lane * nbat;
     const uint32_t cnt = i0 < n ? (n - i0 < nbat ? n - i0 : nbat) : 0u;
     // Uniform trip count: a lane past its share evaluates a dummy entry whose table ORs carry
@@ -1219,6 +1236,7 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
       en = L.lst[ni < (uint32_t)GLIST ? ni : (uint32_t)GLIST - 1u];
       one(check_v, e, b < cnt);
     }
+#endif
   };
 
   // Compact table clear and flush (few active words, no churn): the nf <= 32 active words of
@@ -1287,7 +1305,10 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
     constexpr uint32_t CAP = (uint32_t)GLIST - 1u;
     for (uint32_t lb = 0; lb < total; lb += CAP) {
       const uint32_t nw = total - lb < CAP ? total - lb : CAP;
-      list_bits(L.lst, CAP, f, (uint32_t)lane << 6, pos0 - lb, nw);
+      if (P2PG_LIST_WHOLE && total <= CAP)
+        list_bits_whole(L.lst, CAP, f, (uint32_t)lane << 6, pos0);
+      else
+        list_bits(L.lst, CAP, f, (uint32_t)lane << 6, pos0 - lb, nw);
       wave_lds_sync();
       PROF_MARK(6);
       const uint32_t n = nw;
@@ -1461,7 +1482,10 @@ __device__ __forceinline__ void scatter_wide(const DevGraph& g, const DevState& 
         if (lb + CAP <= s) continue;
         if (lb != have) {
           wave_lds_sync();  // (readers of the window before)
-          list_bits(L.lst, CAP, f, (uint32_t)lane << 6, pos0 - lb, total - lb < CAP ? total - lb : CAP);
+          if (P2PG_LIST_WHOLE && total <= CAP)
+            list_bits_whole(L.lst, CAP, f, (uint32_t)lane << 6, pos0);
+          else
+            list_bits(L.lst, CAP, f, (uint32_t)lane << 6, pos0 - lb, total - lb < CAP ? total - lb : CAP);
           have = lb;
         }
         wave_lds_sync();  // the list and the table clear, before the picks
@@ -1470,11 +1494,27 @@ __device__ __forceinline__ void scatter_wide(const DevGraph& g, const DevState& 
         const uint32_t n = (e < lb + CAP ? e : lb + CAP) - lb - a;
         // strided batches with a uniform trip count, as scatter_row's pick_batch
         const uint32_t nbat = (n + 63) >> 6;
+#if P2PG_PICK_DUP
+        // (a lane past its share re-evaluates valid entries of the sub-list [a, a + n))
+        const uint16_t* q = L.lst + a + pick_first((uint32_t)lane, n, nbat);
+        uint32_t en = *q;
+#else
         const uint32_t i0 = (uint32_t)lane * nbat;
         const uint32_t mine = i0 < n ? (n - i0 < nbat ? n - i0 : nbat) : 0u;
         auto at = [&](uint32_t i) { return a + i < (uint32_t)GLIST ? a + i : (uint32_t)GLIST - 1u; };
         uint32_t en = L.lst[at(i0)];
+#endif
         for (uint32_t b = 0; b < nbat; ++b) {
+#if P2PG_PICK_DUP
+          const uint32_t ent = en;
+          en = *++q;
+          const uint32_t wl = ent >> 6, bit = ent & 63u;
+          const uint32_t mg = p.msg_base + wl * 64u + bit;
+          // the word's rank in the pass: in [0, nr), every entry being one of the pass
+          const uint32_t rr = (uint32_t)__popcll(fam & ((1ull << wl) - 1ull)) - (uint32_t)r0;
+          uint32_t* const col = &L.tbl[rr * 2u + (bit >> 5)];
+          const uint32_t mb = 1u << (bit & 31u);
+#else
           const uint32_t ent = en & 0x0FFFu;  // in range even when stale
           en = L.lst[at(i0 + b + 1)];
           const uint32_t wl = ent >> 6, bit = ent & 63u;
@@ -1484,6 +1524,7 @@ __device__ __forceinline__ void scatter_wide(const DevGraph& g, const DevState& 
                               (uint32_t)(seg - 1);
           uint32_t* const col = &L.tbl[rr * 2u + (bit >> 5)];
           const uint32_t mb = b < mine ? 1u << (bit & 31u) : 0u;
+#endif
           uint32_t pk[K];
           if constexpr (K <= 4)
             gossip_picks_k<K>(pkey, mg, deg, pk);
