@@ -159,6 +159,9 @@ int p2pg_churn_lost(uint32_t round, uint32_t a, uint32_t b, uint32_t threshold, 
  * `round` under the peer's threshold thr (p2pg_set_relay_policy; the exemption of originations is
  * the caller's).                                                                            */
 int p2pg_relay_muted(uint32_t round, uint32_t peer, uint32_t msg, uint32_t thr, uint64_t seed);
+/* 1 iff a peer with the downtime interval [from, until) is offline in round `round`
+ * (p2pg_set_downtime; from = -1: never).                                                    */
+int p2pg_peer_offline(int32_t round, int32_t from, int32_t until);
 
 /* ---- engine ------------------------------------------------------------------------- */
 int p2pg_create(const p2pg_config* cfg, p2pg_engine** out);
@@ -242,6 +245,45 @@ int p2pg_set_ttl(p2pg_engine* e, int32_t M, const int32_t* ttl);
  * touched, and push_form reports the form chosen for that push from the round's own density
  * (P2PG_PUSH_ATOMIC or P2PG_PUSH_EDGE; P2PG_PUSH_ATOMIC in a round that is an expiry round too). */
 int p2pg_set_relay_policy(p2pg_engine* e, int64_t V, const uint32_t* thr, uint64_t seed);
+/* Peer downtime: per-peer, deterministic churn -- offline windows, crashes and late joiners.
+ * Each peer has one half-open interval of rounds [from[v], until[v]): from[v] = -1 never offline,
+ * otherwise 0 <= from[v] < until[v]; until[v] = INT32_MAX never returns (a crash); from[v] = 0
+ * joins late.  Peer v is offline in round r iff from[v] <= r < until[v] (p2pg_peer_offline).
+ * An offline peer keeps its connections: its neighbours have no failure detector and go on
+ * sending to it, and those sends are counted and lost like a send that churn drops (node.py:116
+ * counts before sending).
+ *  1. A send made in round r and addressed to u is lost iff it was lost before (churn, or a
+ *     connection removed at the boundary) or u is offline in round r + 1.  Its sender still
+ *     counts it (round r's relays, sent[v], p2pg_get_sends with lost = 1); it is no arrival
+ *     (round r + 1's received, received[u]) and sets no seen bit at u.  u may still get the
+ *     message later from another copy: an ordinary first receipt of that later round, with the
+ *     later hop and that round's lowest-id sender as parent.
+ *  2. An offline peer has no first receipts, so it sends nothing.  Its seen bits from before
+ *     stand; a receipt it made in round from[v] - 1 sends normally in that round.
+ *  3. Originations at an offline peer are refused, not dropped: P2PG_ERR_ARG from this call when
+ *     a scheduled message (start >= 0) has its source offline in its start round, and from
+ *     p2pg_set_sources, p2pg_set_sources_at and p2pg_originate when a downtime is set and an
+ *     origination falls into its origin's interval.
+ *  4. It composes with flood and gossip, churn, start rounds, hop limits, a relay policy,
+ *     p2pg_update_edges, p2pg_drop_relays, the tallies, the delivery stream and the records: a
+ *     receipt that did not happen is neither expired nor muted.  `active` keeps its rule: a run may
+ *     end while peers are offline, and they do not catch up (there is no anti-entropy).
+ *  5. Every receipt counter follows from the receipts that happened.  `received` is exact iff
+ *     P2PG_FLAG_RECEIVED is set (as under churn); without it a round r with min(from) <= r <
+ *     max(until) reports the sends of round r - 1 (an upper bound) and received_exact = 0.
+ *     p2pg_peer_counters is exact either way.  scatter_words counts the masks pushed towards
+ *     peers that are offline in the next round too (the push happens, the receiver discards it);
+ *     touched_words, and push_form of a round in which somebody is offline, are the engine's.
+ *  6. The downtime belongs to the peers: p2pg_reset and p2pg_set_sources[_at] keep it (subject
+ *     to 3), p2pg_load_csr clears it.  from = NULL or all -1 removes it: the engine then launches
+ *     exactly what it launched before.  V = the engine's peer count.  P2PG_ERR_ARG: another V,
+ *     from[v] < -1, until[v] <= from[v] where from[v] >= 0.  P2PG_ERR_STATE: on a
+ *     vertex-partitioned rank (and p2pg_set_global_ids once a downtime is set), between
+ *     p2pg_step_begin / p2pg_step_end, once a round has run (allowed again after p2pg_reset), and
+ *     p2pg_snapshot / p2pg_restore while one is set.  A rejected call changes nothing.
+ * A round in which somebody is offline takes the unfused schedule (receive pass, the undo of the
+ * offline peers' receipts, push); every other round is planned exactly as without the call. */
+int p2pg_set_downtime(p2pg_engine* e, int64_t V, const int32_t* from, const int32_t* until);
 /* Back to round 0 with the same graph, sources and start rounds (clears seen/frontier state). */
 int p2pg_reset(p2pg_engine* e);
 /* One round. Returns 1 while messages are in flight, 0 when quiescent, < 0 on error. */

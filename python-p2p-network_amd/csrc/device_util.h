@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "downtime.h"
 #include "internal.h"
 #include "philox.h"
 
@@ -108,6 +109,20 @@ __device__ __forceinline__ T* at_row(T* plane, uint64_t r, int W) {
 // Philox keys of churn and gossip are global ids so partitioning cannot change results).
 __device__ __forceinline__ uint32_t gidx(const DevGraph& g, int64_t x) {
   return g.gid ? (uint32_t)g.gid[x] : (uint32_t)x;
+}
+
+// Does the send of round p.round from v to u over slot `slot` of gs never arrive?  (The sends
+// stream, the lost-send count and the peer tallies: relay_sends.hip, relay_tally.hip.)  The
+// connection was removed before the messages arrived, churn dropped the send, or -- peer downtime,
+// d.from set -- the receiver is offline in round p.round + 1 (downtime.h).  An engine without a
+// downtime passes null pointers and runs the first two tests only.
+__device__ __forceinline__ bool send_lost(const DevGraph& gs, const RoundParams& p, const Downtime& d, int64_t v,
+                                          int32_t u, int64_t slot) {
+  if (gs.gone && gs.gone[slot]) return true;
+  if (p.churn_thr &&
+      churn_dropped((uint32_t)p.round, gidx(gs, v), gidx(gs, u), p.churn_thr, p.cseed_lo, p.cseed_hi))
+    return true;
+  return d.from && downtime::offline(p.round + 1, d.from[u], d.until[u]);
 }
 
 // Same for a wave-uniform vertex: a scalar load (see ldc), no vmcnt wait.

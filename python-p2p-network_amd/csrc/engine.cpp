@@ -26,6 +26,10 @@
 //                  scheduled like an expiry round: the muted first receipts' relays leave its
 //                  counters, their frontier bits are cleared when its sends become final, and the
 //                  held-back gossip push then takes the form the round's own density chose
+//   downtime       with peer downtime (p2pg_set_downtime; relay_offline.hip, downtime.h) a round in
+//                  which somebody is offline takes the unfused schedule: the receipts its receive
+//                  pass made at the offline peers are undone right after that pass, and its push
+//                  leaves in the round.  Sends to a peer that is offline in the next round are lost
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +41,7 @@
 #include <vector>
 
 #include "../../include/p2pgpu.h"
+#include "downtime.h"
 #include "internal.h"
 #include "philox.h"
 #include "round_plan.h"
@@ -240,6 +245,15 @@ struct p2pg_engine {
   int32_t pol_pending = -1;      // the policy round whose sends are not final yet (finalize_expiry)
   bool held_push_e = false;      // the pending round's held-back gossip push leaves by edge stores
                                  // (rp::resolve_push at its end), not by row atomics
+  // Peer downtime (p2pg_set_downtime): peer v is offline in the rounds [h_down_from[v],
+  // h_down_until[v]) (empty: no downtime), d_down_from / d_down_until the device copies, uploaded
+  // once by the call.  Like the policy it belongs to the peers and lives and dies with the graph.
+  // down_sweep answers which rounds are offline rounds (downtime.h).
+  std::vector<int32_t> h_down_from, h_down_until;
+  int32_t* d_down_from = nullptr;
+  int32_t* d_down_until = nullptr;
+  bool down_on = false;
+  downtime::Sweep down_sweep;
 };
 
 namespace {
@@ -382,6 +396,12 @@ void free_graph(p2pg_engine* e) {
   dfree(e->d_thr);
   e->h_thr.clear();
   e->pol_on = false;
+  dfree(e->d_down_from);
+  dfree(e->d_down_until);
+  e->h_down_from.clear();
+  e->h_down_until.clear();
+  e->down_sweep.build(0, nullptr, nullptr);
+  e->down_on = false;
   if (e->h_seg_cnt) (void)hipHostFree(e->h_seg_cnt);
   e->h_seg_cnt = nullptr;
   e->auto_buf = nullptr;
@@ -587,13 +607,19 @@ int check_scatter_list(p2pg_engine* e, unsigned long long listed) {
   return P2PG_OK;
 }
 
-// Arrivals (p2pg_round_stats.received): a churn run with P2PG_FLAG_RECEIVED counts the lost sends
-// of every round.
+// Arrivals (p2pg_round_stats.received): a churn or downtime run with P2PG_FLAG_RECEIVED counts the
+// lost sends of every round.
 bool count_lost_on(const p2pg_engine* e) {
-  return e->cfg.churn_threshold != 0 && (e->cfg.flags & P2PG_FLAG_RECEIVED);
+  return (e->cfg.churn_threshold != 0 || e->down_on) && (e->cfg.flags & P2PG_FLAG_RECEIVED);
 }
-// Is the `received` counter exact (no churn, or churn losses counted)?
-bool received_exact(const p2pg_engine* e) { return e->cfg.churn_threshold == 0 || count_lost_on(e); }
+// Is the `received` counter of round r exact?  No churn, or the losses counted; with a downtime
+// whose losses are not counted, every round outside min(from) <= r < max(until).
+bool received_exact(const p2pg_engine* e, int32_t r) {
+  if (count_lost_on(e)) return true;
+  return e->cfg.churn_threshold == 0 && !(e->down_on && e->down_sweep.in_span(r));
+}
+// The device's view of the downtime (null pointers without one: send_lost, device_util.h).
+Downtime down(const p2pg_engine* e) { return Downtime{e->d_down_from, e->d_down_until}; }
 
 // Run tallies (P2PG_FLAG_TALLY): every round keeps its whole frontier rows, which the column
 // count (at the round's end) and the peer pass (before the next round) read.
@@ -612,7 +638,7 @@ hipError_t flush_peer_tally(p2pg_engine* e, const DevGraph& gs) {
   e->tally_pending = -1;
   RoundParams p = params(e);
   p.round = r;
-  return launch_peer_tally(gs, graph_for_arrivals(e, r), e->st, p, e->d_tsent, e->d_trecv, e->stream);
+  return launch_peer_tally(gs, graph_for_arrivals(e, r), e->st, p, down(e), e->d_tsent, e->d_trecv, e->stream);
 }
 
 // Enqueue the count of round r's lost sends (k_sends, count mode) over gs (the graph the sends
@@ -623,7 +649,7 @@ hipError_t enqueue_lost_count(p2pg_engine* e, const DevGraph& gs, const DevGraph
   RoundParams p = params(e);
   p.round = r;
   if (x == hipSuccess)
-    x = launch_sends(gs, gp, e->st, p, false, 0, nullptr, nullptr, nullptr, nullptr, e->d_cnt2, e->stream);
+    x = launch_sends(gs, gp, e->st, p, down(e), false, 0, nullptr, nullptr, nullptr, nullptr, e->d_cnt2, e->stream);
   if (x == hipSuccess)
     x = hipMemcpyAsync(e->h_cnt2, e->d_cnt2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream);
   return x;
@@ -1210,6 +1236,12 @@ int set_sources(p2pg_engine* e, const char* what, int32_t M, const int32_t* src,
   }
   if (late && partitioned(e))
     return fail(e, P2PG_ERR_STATE, w + ": start rounds other than 0 are not available on a vertex-partitioned rank");
+  if (e->down_on) {  // originations at an offline peer are refused (p2pg_set_downtime)
+    const int64_t m = downtime::first_refused(M, src, start, e->h_down_from.data(), e->h_down_until.data());
+    if (m >= 0)
+      return fail(e, P2PG_ERR_ARG, w + ": the origin of message " + std::to_string(m) +
+                                       " is offline in its start round (p2pg_set_downtime)");
+  }
   HIPCHK(e, hipSetDevice(e->cfg.device));
   const int32_t W = (M + 63) / 64;
   e->h_src.assign(src, src + M);
@@ -1268,6 +1300,10 @@ int p2pg_originate(p2pg_engine* e, int64_t n, const int32_t* msg, const int32_t*
   std::sort(ms.begin(), ms.end());
   if (std::adjacent_find(ms.begin(), ms.end()) != ms.end())
     return fail(e, P2PG_ERR_ARG, "originate: a message is listed twice");
+  for (int64_t i = 0; e->down_on && i < n; ++i)
+    if (downtime::offline(round, e->h_down_from[peer[i]], e->h_down_until[peer[i]]))
+      return fail(e, P2PG_ERR_ARG, "originate: peer " + std::to_string(peer[i]) + " is offline in round " +
+                                       std::to_string(round) + " (p2pg_set_downtime)");
   if (n == 0) return P2PG_OK;
   for (int64_t i = 0; i < n; ++i) {
     e->h_src[msg[i]] = peer[i];
@@ -1341,6 +1377,72 @@ int p2pg_set_relay_policy(p2pg_engine* e, int64_t V, const uint32_t* thr, uint64
   }
   e->pol_pending = -1;
   return upload_exempt(e);
+}
+
+int p2pg_set_downtime(p2pg_engine* e, int64_t V, const int32_t* from, const int32_t* until) {
+  if (!e) return fail(e, P2PG_ERR_ARG, "set_downtime: no engine");
+  if (!e->d_rowptr) return fail(e, P2PG_ERR_STATE, "set_downtime: load a graph first");
+  if (V != e->V) return fail(e, P2PG_ERR_ARG, "set_downtime: V differs from the engine's peer count");
+  const bool any = downtime::any(V, from);
+  if (any) {
+    if (!until) return fail(e, P2PG_ERR_ARG, "set_downtime: need until with from");
+    downtime::Bad what = downtime::OK;
+    const int64_t v = downtime::first_bad(V, from, until, &what);
+    if (v >= 0)
+      return fail(e, P2PG_ERR_ARG, "set_downtime: peer " + std::to_string(v) +
+                                       (what == downtime::BAD_FROM ? ": from below -1" : ": until is not above from"));
+  } else {
+    for (int64_t v = 0; from && v < V; ++v)
+      if (from[v] < -1) return fail(e, P2PG_ERR_ARG, "set_downtime: peer " + std::to_string(v) + ": from below -1");
+  }
+  if (partitioned(e))
+    return fail(e, P2PG_ERR_STATE, "set_downtime: peer downtime is not available on a vertex-partitioned rank");
+  if (e->begun) return fail(e, P2PG_ERR_STATE, "set_downtime: a round has begun (step_begin)");
+  if (e->have_state && e->round > 0)
+    return fail(e, P2PG_ERR_STATE, "set_downtime: a round has run (set the downtime before round 0, or after p2pg_reset)");
+  if (!e->failed.empty()) return fail(e, P2PG_ERR_STATE, "set_downtime: " + e->failed);
+  if (any && e->have_state) {  // originations at an offline peer are refused
+    const int64_t m = downtime::first_refused(e->M, e->h_src.data(), e->h_start.data(), from, until);
+    if (m >= 0)
+      return fail(e, P2PG_ERR_ARG, "set_downtime: the origin of message " + std::to_string(m) +
+                                       " would be offline in its start round");
+  }
+  if (!any && !e->down_on) return P2PG_OK;  // nothing set, nothing to remove
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (any) {
+    int32_t *df = nullptr, *du = nullptr;
+    const size_t nb = sizeof(int32_t) * (size_t)V;
+    hipError_t x = hipMalloc((void**)&df, nb);
+    if (x == hipSuccess) x = hipMalloc((void**)&du, nb);
+    if (x == hipSuccess) x = hipMemcpy(df, from, nb, hipMemcpyHostToDevice);
+    if (x == hipSuccess) x = hipMemcpy(du, until, nb, hipMemcpyHostToDevice);
+    if (x != hipSuccess) {
+      if (df) (void)hipFree(df);
+      if (du) (void)hipFree(du);
+      return fail(e, P2PG_ERR_HIP, std::string("set_downtime: ") + hipGetErrorString(x));
+    }
+    dfree(e->d_down_from);
+    dfree(e->d_down_until);
+    e->d_down_from = df;
+    e->d_down_until = du;
+    e->h_down_from.assign(from, from + V);
+    e->h_down_until.assign(until, until + V);
+    e->down_sweep.build(V, from, until);
+    e->down_on = true;
+  } else {  // all -1 (or NULL): the engine without this call
+    dfree(e->d_down_from);
+    dfree(e->d_down_until);
+    e->h_down_from.clear();
+    e->h_down_until.clear();
+    e->down_sweep.build(0, nullptr, nullptr);
+    e->down_on = false;
+  }
+  return P2PG_OK;
+}
+
+int p2pg_peer_offline(int32_t round, int32_t from, int32_t until) {
+  return downtime::offline(round, from, until) ? 1 : 0;
 }
 
 }  // extern "C"
@@ -1519,7 +1621,7 @@ bool close_round(p2pg_engine* e, const uint64_t* tot, int32_t push_form, bool pu
     out->scatter_words = tot[ST_SCATTER];
     out->touched_words = tot[ST_AUX];
     out->push_form = push_form;
-    out->received_exact = received_exact(e) ? 1 : 0;
+    out->received_exact = received_exact(e, e->round) ? 1 : 0;
     out->received = e->round == 0 ? 0 : e->sent_last - e->lost_last;
   }
   rp::advance(e->hist, {tot[ST_NEW], tot[ST_ACTIVE_V], tot[ST_ACTIVE_W], tot[ST_SCATTER]}, pushed_e);
@@ -1616,6 +1718,9 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   facts.origination = orig != nullptr;
   facts.expiry = xi >= 0;
   facts.policy = pol;
+  // Peer downtime: somebody is offline in this round (round 0 has no receive pass, and an
+  // origination at an offline peer is refused, so it has nothing to undo).
+  facts.offline = e->down_on && e->round > 0 && e->down_sweep.offline_round(e->round);
   facts.skip_frontier = e->skip_frontier;
   const rp::RoundPlan plan = rp::plan_round(e->hist, e->rules, caps, facts);
   p.store_f = plan.store_f;
@@ -1665,6 +1770,8 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
         return rc;
       break;
   }
+  if (facts.offline)  // the receipts the pass made at offline peers did not happen (relay_offline.hip)
+    if ((rc = timed(e, 0, [&] { return launch_offline(g, s, p, down(e), e->stream); }))) return rc;
   if (orig)  // Node.send_to_nodes at the origins of this round (node.py:106-112)
     if ((rc = timed(e, 0, [&] {
            return launch_originate(g, s, p, e->d_sched_peer, e->d_sched_msg, e->d_sched_grp, orig->g_lo,
@@ -1810,6 +1917,7 @@ static bool decay_batchable(const p2pg_engine* e) {
   f.consume_next = e->consume_next;
   f.late_starts = e->last_start != 0;
   f.expiry_ahead = expiry_ahead(e, e->round);
+  f.offline_ahead = e->down_on && e->down_sweep.offline_ahead(e->round);
   f.frontier_needed = frontier_needed(e);
   f.autostop = !(e->cfg.flags & P2PG_FLAG_NO_AUTOSTOP);
   f.auto_buf = e->auto_buf != nullptr;
@@ -2029,7 +2137,7 @@ int p2pg_get_sends(p2pg_engine* e, int64_t cap, int32_t* sender, int32_t* receiv
   if (lr == hipSuccess) lr = hipMalloc((void**)&dl, c);
   if (lr == hipSuccess) lr = hipMemsetAsync(e->d_cnt2, 0, 2 * sizeof(unsigned long long), e->stream);
   if (lr == hipSuccess)
-    lr = launch_sends(graph(e), graph_for_arrivals(e, r), e->st, p, true, cap, ds, dr, dm, dl, e->d_cnt2, e->stream);
+    lr = launch_sends(graph(e), graph_for_arrivals(e, r), e->st, p, down(e), true, cap, ds, dr, dm, dl, e->d_cnt2, e->stream);
   unsigned long long cnt = 0;
   if (lr == hipSuccess) lr = hipMemcpyAsync(&cnt, e->d_cnt2, sizeof(cnt), hipMemcpyDeviceToHost, e->stream);
   if (lr == hipSuccess) lr = hipStreamSynchronize(e->stream);
@@ -2286,6 +2394,9 @@ int p2pg_set_global_ids(p2pg_engine* e, const int32_t* gid) {
                                    "vertex-partitioned rank");
   if (gid && e->pol_on)
     return fail(e, P2PG_ERR_STATE, "set_global_ids: a relay policy (p2pg_set_relay_policy) is not available on a "
+                                   "vertex-partitioned rank");
+  if (gid && e->down_on)
+    return fail(e, P2PG_ERR_STATE, "set_global_ids: peer downtime (p2pg_set_downtime) is not available on a "
                                    "vertex-partitioned rank");
   HIPCHK(e, hipSetDevice(e->cfg.device));
   dfree(e->d_gid);
@@ -2753,6 +2864,8 @@ int p2pg_snapshot(p2pg_engine* e, void* buf, int64_t cap) {
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold hop limits (p2pg_set_ttl)");
   if (e->pol_on)
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold a relay policy (p2pg_set_relay_policy)");
+  if (e->down_on)
+    return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold peer downtime (p2pg_set_downtime)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "snapshot: a round has begun (step_begin)");
   if (e->arr_round >= 0 && e->arr_round == e->round)
     return fail(e, P2PG_ERR_STATE, "snapshot: take it before a topology update or after the next round");
@@ -2823,6 +2936,8 @@ int p2pg_restore(p2pg_engine* e, const void* buf, int64_t size) {
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold hop limits (p2pg_set_ttl)");
   if (e->pol_on)
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold a relay policy (p2pg_set_relay_policy)");
+  if (e->down_on)
+    return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold peer downtime (p2pg_set_downtime)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "restore: a round has begun (step_begin)");
   SnapHeader h;
   std::memcpy(&h, buf, sizeof(h));

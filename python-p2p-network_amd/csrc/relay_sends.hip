@@ -28,24 +28,19 @@ __device__ __forceinline__ uint64_t prev_sends(const DevGraph& gp, const DevStat
   return w < st.W ? st.F[prv][(int64_t)y * st.W + w] : 0ull;
 }
 
-__device__ __forceinline__ bool send_lost(const DevGraph& gs, const RoundParams& p, int64_t v, int32_t u,
-                                          int64_t slot) {
-  if (gs.gone && gs.gone[slot]) return true;
-  return p.churn_thr && churn_dropped((uint32_t)p.round, gidx(gs, v), gidx(gs, u), p.churn_thr,
-                                      p.cseed_lo, p.cseed_hi);
-}
-
 // One wave per active peer v of round r = p.round (A[r&1]), lane = word of a 64-word slice.
 // Flood: v sends every first receipt m to each connection over gs but the sender it first got m
 // from -- the lowest-id neighbour over gp whose round-(r-1) send reached it (exclude=[sender],
 // node.py:106-112; none at the origin, r = 0).  Walking v's gp row ascending, `rem` holds the
 // bits whose sender is not found yet; a neighbour y takes rem & (y's sends) as its own.
 // Gossip: one send per Philox pick (the sender is not excluded).
+// A send is lost by send_lost (device_util.h): a removed connection, churn, or a receiver that is
+// offline in round r + 1.
 // EMIT: records at atomic positions (< cap); else only the lost sends are counted (cnt[1]) and
 // peers without a lost connection are skipped.  cnt[0] = sends emitted.
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_sends(DevGraph gs, DevGraph gp, DevState st, RoundParams p,
-                                               int64_t cap, int32_t* __restrict__ snd,
+                                               Downtime d, int64_t cap, int32_t* __restrict__ snd,
                                                int32_t* __restrict__ rcv, int32_t* __restrict__ msg,
                                                uint8_t* __restrict__ lostf,
                                                unsigned long long* __restrict__ cnt) {
@@ -80,7 +75,7 @@ __global__ __launch_bounds__(256) void k_sends(DevGraph gs, DevGraph gp, DevStat
         last_lost = -1;
         for (int64_t j0 = beg; j0 < end; j0 += 64) {
           const int64_t j = j0 + lane;
-          const bool l = j < end && send_lost(gs, p, v, gs.colidx[j], j);
+          const bool l = j < end && send_lost(gs, p, d, v, gs.colidx[j], j);
           const uint64_t bl = __ballot(l);
           if (bl) last_lost = j0 + 63 - __builtin_clzll(bl);
         }
@@ -108,7 +103,7 @@ __global__ __launch_bounds__(256) void k_sends(DevGraph gs, DevGraph gp, DevStat
               if (y == u) break;
             }
             const uint64_t out = f & ~pu;
-            const bool l = send_lost(gs, p, v, u, j);
+            const bool l = send_lost(gs, p, d, v, u, j);
             if (EMIT) {
               uint64_t o = out;
               while (o) {
@@ -135,7 +130,7 @@ __global__ __launch_bounds__(256) void k_sends(DevGraph gs, DevGraph gp, DevStat
             for (int q = 0; q < k; ++q) {
               const int64_t j = beg + ((int)deg > p.fanout ? (int64_t)pk[q] : (int64_t)q);
               const int32_t u = gs.colidx[j];
-              const bool l = send_lost(gs, p, v, u, j);
+              const bool l = send_lost(gs, p, d, v, u, j);
               put(v, u, m, l);
               n_lost += l ? 1u : 0u;
               n_sent += 1u;
@@ -198,13 +193,13 @@ __global__ __launch_bounds__(256) void k_rebuild_aw(DevState st, int32_t round, 
 }  // namespace
 
 hipError_t launch_sends(const DevGraph& gs, const DevGraph& gp, const DevState& st, const RoundParams& p,
-                        bool emit, int64_t cap, int32_t* snd, int32_t* rcv, int32_t* msg, uint8_t* lost,
+                        const Downtime& d, bool emit, int64_t cap, int32_t* snd, int32_t* rcv, int32_t* msg, uint8_t* lost,
                         unsigned long long* cnt, hipStream_t s) {
   const int grid = grid_tasks((gs.V + 31) >> 5);
   if (emit)
-    hipLaunchKernelGGL(k_sends<true>, dim3(grid), dim3(256), 0, s, gs, gp, st, p, cap, snd, rcv, msg, lost, cnt);
+    hipLaunchKernelGGL(k_sends<true>, dim3(grid), dim3(256), 0, s, gs, gp, st, p, d, cap, snd, rcv, msg, lost, cnt);
   else
-    hipLaunchKernelGGL(k_sends<false>, dim3(grid), dim3(256), 0, s, gs, gp, st, p, cap, snd, rcv, msg, lost, cnt);
+    hipLaunchKernelGGL(k_sends<false>, dim3(grid), dim3(256), 0, s, gs, gp, st, p, d, cap, snd, rcv, msg, lost, cnt);
   return hipGetLastError();
 }
 

@@ -189,13 +189,6 @@ __device__ __forceinline__ uint64_t prev_sends(const DevGraph& gp, const DevStat
   return w < st.W ? st.F[prv][(int64_t)y * st.W + w] : 0ull;
 }
 
-__device__ __forceinline__ bool send_lost(const DevGraph& gs, const RoundParams& p, int64_t v, int32_t u,
-                                          int64_t slot) {
-  if (gs.gone && gs.gone[slot]) return true;
-  return p.churn_thr && churn_dropped((uint32_t)p.round, gidx(gs, v), gidx(gs, u), p.churn_thr,
-                                      p.cseed_lo, p.cseed_hi);
-}
-
 // Slot of y in v's ascending gs row, or -1 (wave-uniform arguments).
 __device__ __forceinline__ int64_t find_slot(const DevGraph& gs, int64_t beg, int64_t end, int32_t y) {
   int64_t lo = beg, hi = end;
@@ -207,7 +200,7 @@ __device__ __forceinline__ int64_t find_slot(const DevGraph& gs, int64_t beg, in
 }
 
 // sent[v] += the send_to_node calls of v's round-r first receipts, received[u] += those of them
-// addressed to u that are not lost (churn, or a slot gs.gone marks).  One wave per active peer v
+// addressed to u that are not lost (send_lost, device_util.h).  One wave per active peer v
 // of round r = p.round, lane = word of a 64-word slice, the send set of k_sends:
 // Flood: all n bits of a slice go to every connection (lane-parallel over the connections: one
 //   add of n per connection), less, for r > 0, each bit's sender -- the lowest-id neighbour over
@@ -220,6 +213,7 @@ __device__ __forceinline__ int64_t find_slot(const DevGraph& gs, int64_t beg, in
 //   per connection in the wave's LDS table (rows of at most HUB_T connections), so the global
 //   atomics are one per connection that was picked; wider rows add per pick.
 __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, DevState st, RoundParams p,
+                                                    Downtime d,
                                                     unsigned long long* __restrict__ sent,
                                                     unsigned long long* __restrict__ received) {
   __shared__ uint32_t tab_all[WPB][HUB_T];
@@ -260,7 +254,7 @@ __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, De
             const int64_t j = j0 + lane;
             if (j < end) {
               const int32_t u = gs.colidx[j];
-              if (!send_lost(gs, p, v, u, j)) atomicAdd(received + u, (unsigned long long)n);
+              if (!send_lost(gs, p, d, v, u, j)) atomicAdd(received + u, (unsigned long long)n);
             }
           }
           v_sent += (unsigned long long)n * deg;
@@ -278,7 +272,7 @@ __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, De
               const int64_t j = same ? jp : find_slot(gs, beg, end, y);
               if (j < 0) continue;  // no longer a connection: nothing was sent to it
               v_sent -= c;
-              if (lane == 0 && !send_lost(gs, p, v, y, j)) atomicAdd(received + y, 0ull - (unsigned long long)c);
+              if (lane == 0 && !send_lost(gs, p, d, v, y, j)) atomicAdd(received + y, 0ull - (unsigned long long)c);
             }
           }
         } else {
@@ -299,7 +293,7 @@ __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, De
             } else {
               const int64_t j = beg + (int64_t)pick;
               const int32_t u = gs.colidx[j];
-              if (!send_lost(gs, p, v, u, j)) atomicAdd(received + u, 1ull);
+              if (!send_lost(gs, p, d, v, u, j)) atomicAdd(received + u, 1ull);
             }
           };
           auto draw = [&](auto kc) {  // fanout <= 4: one Philox block per receipt, picks in registers
@@ -336,7 +330,7 @@ __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, De
           if (c) {
             const int64_t j = beg + i;
             const int32_t u = gs.colidx[j];
-            if (!send_lost(gs, p, v, u, j)) atomicAdd(received + u, (unsigned long long)c);
+            if (!send_lost(gs, p, d, v, u, j)) atomicAdd(received + u, (unsigned long long)c);
           }
         }
         wave_lds_sync();
@@ -374,8 +368,8 @@ hipError_t launch_column_count(const uint64_t* plane, const uint32_t* A, int64_t
 }
 
 hipError_t launch_peer_tally(const DevGraph& gs, const DevGraph& gp, const DevState& st, const RoundParams& p,
-                             unsigned long long* sent, unsigned long long* received, hipStream_t s) {
-  hipLaunchKernelGGL(k_peer_tally, dim3(grid_tasks((gs.V + 31) >> 5)), dim3(256), 0, s, gs, gp, st, p, sent,
+                             const Downtime& d, unsigned long long* sent, unsigned long long* received, hipStream_t s) {
+  hipLaunchKernelGGL(k_peer_tally, dim3(grid_tasks((gs.V + 31) >> 5)), dim3(256), 0, s, gs, gp, st, p, d, sent,
                      received);
   return hipGetLastError();
 }

@@ -85,6 +85,7 @@ SIGNATURES = {
     "p2pg_gossip_targets": (ctypes.c_int, [_U32, _U32, _U32, _U32, _I32, _U64, _P]),
     "p2pg_churn_lost": (ctypes.c_int, [_U32, _U32, _U32, _U32, _U64]),
     "p2pg_relay_muted": (ctypes.c_int, [_U32, _U32, _U32, _U32, _U64]),
+    "p2pg_peer_offline": (ctypes.c_int, [_I32, _I32, _I32]),
     "p2pg_create": (ctypes.c_int, [ctypes.POINTER(Config), _PP]),
     "p2pg_load_csr": (ctypes.c_int, [_P, _I64, _P, _P]),
     "p2pg_set_sources": (ctypes.c_int, [_P, _I32, _P]),
@@ -92,6 +93,7 @@ SIGNATURES = {
     "p2pg_originate": (ctypes.c_int, [_P, _I64, _P, _P, _I32]),
     "p2pg_set_ttl": (ctypes.c_int, [_P, _I32, _P]),
     "p2pg_set_relay_policy": (ctypes.c_int, [_P, _I64, _P, _U64]),
+    "p2pg_set_downtime": (ctypes.c_int, [_P, _I64, _P, _P]),
     "p2pg_reset": (ctypes.c_int, [_P]),
     "p2pg_step": (ctypes.c_int, [_P, ctypes.POINTER(RoundStatsC)]),
     "p2pg_run": (ctypes.c_int, [_P, _I32, _P, ctypes.POINTER(_I32)]),

@@ -109,6 +109,9 @@ PeerCounters = namedtuple("PeerCounters", "sent received")
 # consume/has_next 8, gossip_seed 9, churn_seed 10, graph_hash 11, src_hash 12, total_relays 13)
 _SNAP_TOTAL_RELAYS_WORD = 13
 
+# p2pg_set_downtime: until = INT32_MAX, a peer that never returns
+_FOREVER = 0x7FFFFFFF
+
 
 def churn_threshold(p_drop):
     """floor(p_drop * 2^32), the integer threshold of the per-round edge-drop mask."""
@@ -164,6 +167,8 @@ class GraphNetwork:
         self.ttl = None              # int32 [M]: each broadcast's hop limit (-1 = unlimited)
         self.relay_thr = None        # uint32 [V]: the relay policy's mute thresholds (None = no policy)
         self.relay_seed = 0
+        self.offline_from = None     # int32 [V]: the peers' downtime intervals [from, until)
+        self.offline_until = None    # (None = no downtime; until 0x7FFFFFFF = forever)
         self._autostop = bool(autostop)
         self._next_round = 0         # the next round the engine runs
         self._quiet = False          # the engine went quiet (further steps run no round)
@@ -305,6 +310,42 @@ class GraphNetwork:
                                                      ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)))
         self.relay_thr = t if t is not None and t.any() else None
         self.relay_seed = int(seed) & 0xFFFFFFFFFFFFFFFF if self.relay_thr is not None else 0
+
+    @staticmethod
+    def peer_offline(round, offline_from, offline_until):
+        """Is a peer with the downtime interval [``offline_from``, ``offline_until``) offline in
+        ``round``?  (p2pg_peer_offline; ``offline_from`` -1 = never, ``offline_until`` None or -1 =
+        forever.)"""
+        until = _FOREVER if offline_until is None or int(offline_until) == -1 else int(offline_until)
+        return bool(_lib.lib().p2pg_peer_offline(int(round), int(offline_from), until))
+
+    def set_downtime(self, offline_from, offline_until=None):
+        """Per-peer downtime, before round 0 runs (or after ``reset``): peer v is offline in the
+        rounds ``offline_from[v] <= r < offline_until[v]`` (``offline_from[v]`` = -1: never; 0: it
+        joins late; ``offline_until`` None, or -1 entries: forever, a crash).  An offline peer keeps
+        its connections: its neighbours go on sending to it, and those sends are counted by their
+        senders and lost.  It has no first receipts and sends nothing; after its return it may
+        still get a message from a later copy.  Originations at an offline peer are refused.
+        ``set_downtime(None)`` (or all -1) removes it.  ``reset`` and ``broadcast`` keep it
+        (p2pg_set_downtime)."""
+        V = self.graph.V
+        if offline_from is None:
+            self._check(_lib.lib().p2pg_set_downtime(self._h, V, None, None))
+            self.offline_from = self.offline_until = None
+            return
+        f = np.array(offline_from, dtype=np.int64, ndmin=1)
+        u = np.full(V, -1, dtype=np.int64) if offline_until is None else np.array(offline_until, dtype=np.int64, ndmin=1)
+        if f.shape != (V,) or u.shape != (V,):
+            raise ValueError("offline_from / offline_until must hold one round per peer")
+        u = np.where(u == -1, _FOREVER, u)
+        if ((f < -(1 << 31)) | (f > _FOREVER) | (u < -(1 << 31)) | (u > _FOREVER)).any():
+            raise ValueError("offline_from / offline_until must be int32 rounds")
+        f = np.ascontiguousarray(f, dtype=np.int32)
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        self._check(_lib.lib().p2pg_set_downtime(self._h, V, _lib.ptr(f), _lib.ptr(u)))
+        on = bool((f >= 0).any())
+        self.offline_from = f if on else None
+        self.offline_until = u if on else None
 
     def originate(self, msgs, peers, round=None):
         """Between rounds: start the unscheduled broadcasts ``msgs`` at ``peers`` in ``round``

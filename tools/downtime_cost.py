@@ -1,0 +1,98 @@
+#!/usr/bin/env python
+"""What peer downtime costs: JSON lines for
+
+  * config 3's flood (1M-peer G(n,p), mean degree 16, 4096 broadcasts) and a 1M-peer
+    Barabasi-Albert (m = 4) push-gossip with 4096 broadcasts and fanout 3 (tools/policy_cost.py's
+    shapes),
+  * each run three times: without a downtime, with 1 % of the peers crashing in round 5 (every
+    later round is then an offline round: the gossip arm pays the unfused schedule to the end),
+    and with 10 % of the peers in a two-round outage (rounds 5 and 6: two offline rounds, the fused
+    rounds come back after them),
+
+with host wall ms per reset + run, rounds, relays, first receipts and the push forms of the rounds,
+each against the no-downtime arm of the same session.  No origin carries an interval.
+
+Device time of k_offline (one launch per offline round, right after the receive pass) comes from
+running this tool under `rocprofv3 --kernel-trace --stats -- python tools/downtime_cost.py ...`.
+
+    python tools/downtime_cost.py [--peers 1000000] [--msgs 4096] [--steps 3]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "python-p2p-network_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--peers", type=int, default=1_000_000)
+    ap.add_argument("--msgs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--only", default="", help="c3_flood or ba_gossip (default: both)")
+    args = ap.parse_args()
+    import numpy as np
+    from p2pnetwork.gpu import GraphNetwork, PeerGraph, make_sources
+    from p2pnetwork.gpu.network import PUSH_FORMS
+    M = args.msgs
+    cases = (("c3_flood", lambda: PeerGraph.gnp(args.peers, 16, seed=1), dict(mode="flood")),
+             ("ba_gossip", lambda: PeerGraph.barabasi_albert(args.peers, 4, seed=1),
+              dict(mode="gossip", fanout=3, gossip_seed=0x5EED)))
+    for name, graph, kw in cases:
+        if args.only and args.only != name:
+            continue
+        g = graph()
+        src = make_sources(g.V, M, seed=1)
+        free = np.setdiff1d(np.arange(g.V), src)  # (originations at an offline peer are refused)
+        pick = np.random.default_rng(1).permutation(free)
+
+        def schedule(n, a, b):
+            f = np.full(g.V, -1, dtype=np.int32)
+            u = np.full(g.V, 0x7FFFFFFF, dtype=np.int32)
+            f[pick[:n]], u[pick[:n]] = a, b
+            return f, u
+        arms = (("none", None), ("crash_1pct_round5", schedule(g.V // 100, 5, 0x7FFFFFFF)),
+                ("outage_10pct_rounds5_6", schedule(g.V // 10, 5, 7)))
+        base = None
+        for arm, down in arms:
+            with GraphNetwork(g, **kw) as net:
+                net.broadcast(src)
+                if down is not None:
+                    net.set_downtime(*down)
+                net.run()  # warm-up (first launches, the spare seen plane)
+                ms = []
+                for _ in range(args.steps):
+                    t0 = time.perf_counter()
+                    net.reset()
+                    rounds = net.run()
+                    ms.append((time.perf_counter() - t0) * 1e3)
+                relays = sum(r.relays for r in rounds)
+                forms = {}
+                for r in rounds:
+                    forms[PUSH_FORMS[r.push_form]] = forms.get(PUSH_FORMS[r.push_form], 0) + 1
+                med = float(np.median(ms))
+                line = {"what": name, "arm": arm, "peers": g.V, "msgs": M, "W": (M + 63) // 64,
+                        "rounds": len(rounds), "relays": relays,
+                        "delivered": int(sum(r.new_deliveries for r in rounds)),
+                        "ms_per_run": [round(x, 3) for x in ms], "ms_median": round(med, 3),
+                        "gteps": round(relays / (med * 1e-3) / 1e9, 2), "push_forms": forms,
+                        "push_form_per_round": "".join(PUSH_FORMS[r.push_form][0] for r in rounds)}
+                if down is None:
+                    base = line
+                else:
+                    f, u = down
+                    line["offline_peers"] = int((f >= 0).sum())
+                    last = int(u[f >= 0].max())  # (one window: every round from 5 to the last until)
+                    line["offline_rounds"] = int(sum(1 for r in rounds if 5 <= r.round < last))
+                    line["ms_vs_none"] = round(med / base["ms_median"], 3)
+                    line["delivered_vs_none"] = round(line["delivered"] / base["delivered"], 4)
+                print(json.dumps(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()
