@@ -130,6 +130,19 @@ typedef struct p2pg_round_stats {
                                 nodeconnection.py:215; duplicates included, 0 at round 0)  */
 } p2pg_round_stats;
 
+/* One anti-entropy exchange (p2pg_set_anti_entropy, p2pg_get_pull_stats): the requests of round
+ * request_round, their replies of the round after, and what the replies repaired in the round
+ * after that.  Pull packets are counted here only, never in the relay counters.              */
+typedef struct p2pg_pull_stats {
+  int32_t request_round;
+  int32_t reserved;
+  uint64_t requests;       /* request packets sent (one per online peer with a connection)      */
+  uint64_t requests_lost;  /* ... lost: churn, or the partner offline in request_round + 1       */
+  uint64_t replies;        /* reply packets sent = requests that arrived (empty replies too)     */
+  uint64_t replies_lost;   /* ... lost: churn, or the requester offline in request_round + 2     */
+  uint64_t repaired;       /* first receipts of request_round + 2 that no relay copy delivered   */
+} p2pg_pull_stats;
+
 /* ---- graphs (host side; no GPU needed) ---------------------------------------------- */
 /* kind: 0 random d-regular (a = d), 1 G(n,p) with p = a / (V-1) (a = mean degree),
  *       2 Barabasi-Albert (a = m, initial (m+1)-clique), 3 Watts-Strogatz (a = k, b = beta),
@@ -162,6 +175,10 @@ int p2pg_relay_muted(uint32_t round, uint32_t peer, uint32_t msg, uint32_t thr, 
 /* 1 iff a peer with the downtime interval [from, until) is offline in round `round`
  * (p2pg_set_downtime; from = -1: never).                                                    */
 int p2pg_peer_offline(int32_t round, int32_t from, int32_t until);
+/* The slot, in its ascending connection list of length deg >= 1, of the connection `peer` sends its
+ * anti-entropy request of round `round` to under the key `seed` (p2pg_set_anti_entropy):
+ * lemire32(philox4x32_10((round, peer, 0, 'AEP'), seed).x, deg).  -1 for deg = 0.            */
+int32_t p2pg_pull_partner_slot(uint32_t round, uint32_t peer, uint32_t deg, uint64_t seed);
 
 /* ---- engine ------------------------------------------------------------------------- */
 int p2pg_create(const p2pg_config* cfg, p2pg_engine** out);
@@ -267,7 +284,7 @@ int p2pg_set_relay_policy(p2pg_engine* e, int64_t V, const uint32_t* thr, uint64
  *  4. It composes with flood and gossip, churn, start rounds, hop limits, a relay policy,
  *     p2pg_update_edges, p2pg_drop_relays, the tallies, the delivery stream and the records: a
  *     receipt that did not happen is neither expired nor muted.  `active` keeps its rule: a run may
- *     end while peers are offline, and they do not catch up (there is no anti-entropy).
+ *     end while peers are offline, and they do not catch up (unless p2pg_set_anti_entropy is set).
  *  5. Every receipt counter follows from the receipts that happened.  `received` is exact iff
  *     P2PG_FLAG_RECEIVED is set (as under churn); without it a round r with min(from) <= r <
  *     max(until) reports the sends of round r - 1 (an upper bound) and received_exact = 0.
@@ -284,6 +301,51 @@ int p2pg_set_relay_policy(p2pg_engine* e, int64_t V, const uint32_t* thr, uint64
  * A round in which somebody is offline takes the unfused schedule (receive pass, the undo of the
  * offline peers' receipts, push); every other round is planned exactly as without the call. */
 int p2pg_set_downtime(p2pg_engine* e, int64_t V, const int32_t* from, const int32_t* until);
+/* Anti-entropy: periodic pull repair, the other half of epidemic broadcast.  An exchange happens in
+ * every request round r with first <= r <= last and (r - first) % period == 0 and takes three
+ * rounds (the reference app: a request queue on the dedup relay's Node, the harness's round being
+ * arrivals, originations, replies, requests):
+ *  1. Round r, after its arrivals and originations: every peer u that is online in r and has a
+ *     connection sends one request to the connection in slot p2pg_pull_partner_slot(r, u, deg(u),
+ *     seed) of its ascending list, carrying its seen set of that moment.  There is no failure
+ *     detector: u may pick an offline neighbour.  The request is a send of round r: lost by the
+ *     churn draw of (r, {u, p}) or because p is offline in r + 1.
+ *  2. Round r + 1, at the partner p, after that round's arrivals and originations: one reply per
+ *     request that arrived, listing every message p has seen by then that the digest lacks -- sent
+ *     even if that list is empty, so replies = requests that arrived.  A send of round r + 1: lost
+ *     by the churn draw of (r + 1, {p, u}) or because u is offline in r + 2.
+ *  3. Round r + 2, at u: the reply is one more arriving packet from sender p, processed in
+ *     ascending sender order after p's relay packets.  Every listed message u has not seen is an
+ *     ordinary first receipt of round r + 2: hop r + 2, parent = the lowest-id sender whose copy
+ *     arrived (min of the lowest relay sender and p), relayed like any other (flood: every
+ *     connection but that sender; gossip: its k picks of round r + 2).  What p itself receives in
+ *     round r + 2 is not visible to u in that round.
+ *  4. relays, received, the per-peer counters and p2pg_get_sends stay what they are -- relay
+ *     packets only, those of pulled first receipts included.  Pull packets are recorded per
+ *     exchange (p2pg_get_pull_stats).  new_deliveries and the other receipt counters of round r + 2
+ *     include the pulled receipts.
+ *  5. `active` (and so p2pg_run) stays 1 while a request round lies at or ahead or an exchange is
+ *     in flight, besides packets and starts ahead; `last` is mandatory, so a run ends.
+ *  6. It composes with flood and gossip, churn, start rounds, p2pg_originate, peer downtime, the
+ *     tallies, the records, the delivery stream and p2pg_get_sends.  The setting belongs to the
+ *     peers: p2pg_reset and p2pg_set_sources[_at] keep it, p2pg_load_csr clears it.  period = 0
+ *     removes it (first, last and seed are then ignored): the engine launches exactly what it
+ *     launched before.
+ * P2PG_ERR_ARG: first < 0, last < first, period < 0.  P2PG_ERR_STATE: once a round has run (allowed
+ * again after p2pg_reset), between p2pg_step_begin / p2pg_step_end, and on a vertex-partitioned
+ * rank (p2pg_set_global_ids while it is set likewise).  While it is set, p2pg_snapshot /
+ * p2pg_restore, p2pg_update_edges and p2pg_drop_relays return P2PG_ERR_STATE.  Not together with a
+ * finite hop limit, in either call order (P2PG_ERR_STATE from the second call): under the
+ * reference's ttl - 1 app a pulled message carries the budget its holder had left, which is not a
+ * function of the round, so the engine's round-based expiry would be wrong.  Not together with a
+ * relay policy either (P2PG_ERR_STATE, either order): whether a muted peer answers requests is a
+ * policy question of its own and out of scope here.  A rejected call changes nothing.
+ * Only the arrival rounds r + 2 launch anything (two passes around the receive pass, unfused
+ * schedule); request and reply rounds are planned exactly as without the call.              */
+int p2pg_set_anti_entropy(p2pg_engine* e, int32_t first, int32_t last, int32_t period, uint64_t seed);
+/* The records of the exchanges completed in this run (since p2pg_reset / the sources), in order of
+ * request round: up to cap of them into out, *n_out = their number.                            */
+int p2pg_get_pull_stats(p2pg_engine* e, int64_t cap, p2pg_pull_stats* out, int64_t* n_out);
 /* Back to round 0 with the same graph, sources and start rounds (clears seen/frontier state). */
 int p2pg_reset(p2pg_engine* e);
 /* One round. Returns 1 while messages are in flight, 0 when quiescent, < 0 on error. */
@@ -358,7 +420,9 @@ int p2pg_message_tally(p2pg_engine* e, uint64_t* reach, uint64_t* hop_sum, int32
  * a boundary.  p2pg_reset and p2pg_set_sources zero all tallies. */
 int p2pg_peer_counters(p2pg_engine* e, uint64_t* sent, uint64_t* received);
 /* Summed device time per kernel class since the last reset (needs P2PG_FLAG_TIMING):
- * 0 seed (origination, in round 0 and later; the hop-limit passes of expiry rounds), 1 flood pull, 2 gossip scatter by row atomics (sparse rounds),
+ * 0 seed (origination, in round 0 and later; the hop-limit passes of expiry rounds; the relay-policy
+ * and downtime passes; the two anti-entropy passes of arrival rounds, k_pull_gather and
+ * k_pull_apply -- an anti-entropy run's repair time shows up in this class), 1 flood pull, 2 gossip scatter by row atomics (sparse rounds),
  * 3 record (validation), 4 gossip update (consume row atomics), 5 gossip pull (consume edge
  * stores), 6 gossip scatter by edge stores (dense rounds), 7 gossip fused pull + scatter
  * (a dense round after a dense round).                                                  */

@@ -125,6 +125,20 @@ __device__ __forceinline__ bool send_lost(const DevGraph& gs, const RoundParams&
   return d.from && downtime::offline(p.round + 1, d.from[u], d.until[u]);
 }
 
+// Anti-entropy: the connection peer v (deg >= 1) sent its request of round `rr` to (philox.h).
+__device__ __forceinline__ int32_t pull_partner(const DevGraph& g, const Pull& pl, int32_t rr, int64_t v) {
+  const int64_t beg = g.rowptr[v];
+  const uint32_t deg = (uint32_t)(g.rowptr[v + 1] - beg);
+  return g.colidx[beg + pull_partner_slot((uint32_t)rr, gidx(g, v), deg, pl.seed_lo, pl.seed_hi)];
+}
+
+// The messages the reply that arrived at v in the arrival round being worked on carried in word w
+// (0: not an arrival round, no reply, or nothing in it).
+__device__ __forceinline__ uint64_t pull_word(const DevState& st, const Pull& pl, int64_t v, int w) {
+  if (!pl.R || w >= st.W || !bit_test(pl.PB, v)) return 0ull;
+  return pl.R[v * st.W + w];
+}
+
 // Same for a wave-uniform vertex: a scalar load (see ldc), no vmcnt wait.
 __device__ __forceinline__ uint32_t gidx_s(const DevGraph& g, int64_t x) {
   const int64_t xu = __builtin_amdgcn_readfirstlane((int)x);

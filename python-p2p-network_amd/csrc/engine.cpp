@@ -30,6 +30,11 @@
 //                  which somebody is offline takes the unfused schedule: the receipts its receive
 //                  pass made at the offline peers are undone right after that pass, and its push
 //                  leaves in the round.  Sends to a peer that is offline in the next round are lost
+//   anti-entropy   with periodic pull repair (p2pg_set_anti_entropy; relay_pull.hip, anti_entropy.h)
+//                  the round in which an exchange's replies arrive takes the unfused schedule too:
+//                  the reply plane is gathered before its receive pass, and what the replies carried
+//                  and no relay copy delivered joins its first receipts after that pass.  Request
+//                  and reply rounds launch nothing
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,6 +46,7 @@
 #include <vector>
 
 #include "../../include/p2pgpu.h"
+#include "anti_entropy.h"
 #include "downtime.h"
 #include "internal.h"
 #include "philox.h"
@@ -254,6 +260,18 @@ struct p2pg_engine {
   int32_t* d_down_until = nullptr;
   bool down_on = false;
   downtime::Sweep down_sweep;
+  // Anti-entropy (p2pg_set_anti_entropy; anti_entropy.h, relay_pull.hip): the request rounds and
+  // the partner draw's key.  The reply plane, its bitmap and the exchange's counter shards exist
+  // only while it is set (with a state: they are sized by W).  pull_round = the arrival round the
+  // plane belongs to (-1: none yet); pull_log = the exchanges completed in this run.
+  anti_entropy::Setting ae;
+  uint64_t ae_seed = 0;
+  uint64_t* d_pull_R = nullptr;
+  uint32_t* d_pull_PB = nullptr;
+  unsigned long long* d_pull_cnt = nullptr;
+  unsigned long long* h_pull_cnt = nullptr;  // pinned, [STAT_SHARDS][PULL_N]
+  int32_t pull_round = -1;
+  std::vector<p2pg_pull_stats> pull_log;
 };
 
 namespace {
@@ -279,6 +297,18 @@ template <class T>
 void dfree(T*& p) {
   if (p) (void)hipFree(p);
   p = nullptr;
+}
+
+// Anti-entropy: the reply plane, its bitmap and the counter shards (allocated at the first arrival
+// round: ensure_pull), and what the run recorded.
+void free_pull(p2pg_engine* e) {
+  dfree(e->d_pull_R);
+  dfree(e->d_pull_PB);
+  dfree(e->d_pull_cnt);
+  if (e->h_pull_cnt) (void)hipHostFree(e->h_pull_cnt);
+  e->h_pull_cnt = nullptr;
+  e->pull_round = -1;
+  e->pull_log.clear();
 }
 
 void free_state(p2pg_engine* e) {
@@ -342,6 +372,7 @@ void free_state(p2pg_engine* e) {
   dfree(e->d_pex);  // (the policy itself stays with the graph: free_graph)
   e->pex_rounds.clear();
   e->pol_pending = -1;
+  free_pull(e);  // (sized by W; the setting itself stays with the graph: free_graph)
   e->have_state = false;
 }
 
@@ -402,6 +433,9 @@ void free_graph(p2pg_engine* e) {
   e->h_down_until.clear();
   e->down_sweep.build(0, nullptr, nullptr);
   e->down_on = false;
+  free_pull(e);
+  e->ae = anti_entropy::Setting{};
+  e->ae_seed = 0;
   if (e->h_seg_cnt) (void)hipHostFree(e->h_seg_cnt);
   e->h_seg_cnt = nullptr;
   e->auto_buf = nullptr;
@@ -620,6 +654,30 @@ bool received_exact(const p2pg_engine* e, int32_t r) {
 }
 // The device's view of the downtime (null pointers without one: send_lost, device_util.h).
 Downtime down(const p2pg_engine* e) { return Downtime{e->d_down_from, e->d_down_until}; }
+// The device's view of the anti-entropy exchange whose replies arrived in round r: the reply plane
+// while it still belongs to that round (until the next gather), else null pointers -- find_parent
+// and the sender walks of k_sends / k_peer_tally then do what they do without the setting.
+Pull pull_of(const p2pg_engine* e, int32_t r) {
+  if (!e->ae.on() || !e->d_pull_R || r < 0 || e->pull_round != r) return Pull{nullptr, nullptr, nullptr, 0u, 0u};
+  return Pull{e->d_pull_R, e->d_pull_PB, e->d_pull_cnt, (uint32_t)e->ae_seed, (uint32_t)(e->ae_seed >> 32)};
+}
+
+constexpr size_t PULL_BYTES = sizeof(unsigned long long) * STAT_SHARDS * PULL_N;
+// The reply plane, its bitmap and the counter shards, allocated at the first arrival round of a
+// state (they are sized by its W) and freed with it.
+int ensure_pull(p2pg_engine* e) {
+  if (e->d_pull_R) return P2PG_OK;
+  hipError_t x = hipMalloc((void**)&e->d_pull_R, e->plane_bytes ? e->plane_bytes : 8);
+  if (x == hipSuccess) x = hipMalloc((void**)&e->d_pull_PB, e->bm_bytes ? e->bm_bytes : 8);
+  if (x == hipSuccess) x = hipMalloc((void**)&e->d_pull_cnt, PULL_BYTES);
+  if (x == hipSuccess) x = hipHostMalloc((void**)&e->h_pull_cnt, PULL_BYTES);
+  if (x == hipSuccess) return P2PG_OK;
+  dfree(e->d_pull_R);
+  dfree(e->d_pull_PB);
+  dfree(e->d_pull_cnt);
+  return fail(e, x == hipErrorOutOfMemory ? P2PG_ERR_NOMEM : P2PG_ERR_HIP,
+              std::string("step (anti-entropy planes): ") + hipGetErrorString(x));
+}
 
 // Run tallies (P2PG_FLAG_TALLY): every round keeps its whole frontier rows, which the column
 // count (at the round's end) and the peer pass (before the next round) read.
@@ -638,7 +696,7 @@ hipError_t flush_peer_tally(p2pg_engine* e, const DevGraph& gs) {
   e->tally_pending = -1;
   RoundParams p = params(e);
   p.round = r;
-  return launch_peer_tally(gs, graph_for_arrivals(e, r), e->st, p, down(e), e->d_tsent, e->d_trecv, e->stream);
+  return launch_peer_tally(gs, graph_for_arrivals(e, r), e->st, p, down(e), pull_of(e, r), e->d_tsent, e->d_trecv, e->stream);
 }
 
 // Enqueue the count of round r's lost sends (k_sends, count mode) over gs (the graph the sends
@@ -649,7 +707,7 @@ hipError_t enqueue_lost_count(p2pg_engine* e, const DevGraph& gs, const DevGraph
   RoundParams p = params(e);
   p.round = r;
   if (x == hipSuccess)
-    x = launch_sends(gs, gp, e->st, p, down(e), false, 0, nullptr, nullptr, nullptr, nullptr, e->d_cnt2, e->stream);
+    x = launch_sends(gs, gp, e->st, p, down(e), pull_of(e, r), false, 0, nullptr, nullptr, nullptr, nullptr, e->d_cnt2, e->stream);
   if (x == hipSuccess)
     x = hipMemcpyAsync(e->h_cnt2, e->d_cnt2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream);
   return x;
@@ -1332,6 +1390,9 @@ int p2pg_set_ttl(p2pg_engine* e, int32_t M, const int32_t* ttl) {
   if (e->begun) return fail(e, P2PG_ERR_STATE, "set_ttl: a round has begun (step_begin)");
   if (e->round > 0) return fail(e, P2PG_ERR_STATE, "set_ttl: a round has run (set the hop limits before round 0, or after p2pg_reset)");
   if (!e->failed.empty()) return fail(e, P2PG_ERR_STATE, "set_ttl: " + e->failed);
+  if (finite && e->ae.on())
+    return fail(e, P2PG_ERR_STATE, "set_ttl: hop limits are not available together with anti-entropy "
+                                   "(p2pg_set_anti_entropy): a pulled message's remaining budget is no function of the round");
   if (!finite && e->h_ttl.empty()) return P2PG_OK;  // nothing set, nothing to remove
   if (finite)
     e->h_ttl.assign(ttl, ttl + M);
@@ -1353,6 +1414,9 @@ int p2pg_set_relay_policy(p2pg_engine* e, int64_t V, const uint32_t* thr, uint64
   if (!e->failed.empty()) return fail(e, P2PG_ERR_STATE, "set_relay_policy: " + e->failed);
   bool any = false;
   for (int64_t v = 0; thr && v < V; ++v) any |= thr[v] != 0u;
+  if (any && e->ae.on())
+    return fail(e, P2PG_ERR_STATE, "set_relay_policy: a relay policy is not available together with anti-entropy "
+                                   "(p2pg_set_anti_entropy)");
   if (!any && !e->pol_on) return P2PG_OK;  // nothing set, nothing to remove
   HIPCHK(e, hipSetDevice(e->cfg.device));
   HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -1443,6 +1507,57 @@ int p2pg_set_downtime(p2pg_engine* e, int64_t V, const int32_t* from, const int3
 
 int p2pg_peer_offline(int32_t round, int32_t from, int32_t until) {
   return downtime::offline(round, from, until) ? 1 : 0;
+}
+
+int p2pg_set_anti_entropy(p2pg_engine* e, int32_t first, int32_t last, int32_t period, uint64_t seed) {
+  if (!e) return fail(e, P2PG_ERR_ARG, "set_anti_entropy: no engine");
+  if (!e->d_rowptr) return fail(e, P2PG_ERR_STATE, "set_anti_entropy: load a graph first");
+  switch (anti_entropy::check(first, last, period)) {
+    case anti_entropy::BAD_PERIOD: return fail(e, P2PG_ERR_ARG, "set_anti_entropy: period below 0");
+    case anti_entropy::BAD_FIRST: return fail(e, P2PG_ERR_ARG, "set_anti_entropy: first below 0");
+    case anti_entropy::BAD_LAST: return fail(e, P2PG_ERR_ARG, "set_anti_entropy: last below first");
+    case anti_entropy::OK: break;
+  }
+  if (partitioned(e))
+    return fail(e, P2PG_ERR_STATE, "set_anti_entropy: anti-entropy is not available on a vertex-partitioned rank");
+  if (e->begun) return fail(e, P2PG_ERR_STATE, "set_anti_entropy: a round has begun (step_begin)");
+  if (e->have_state && e->round > 0)
+    return fail(e, P2PG_ERR_STATE, "set_anti_entropy: a round has run (set it before round 0, or after p2pg_reset)");
+  if (!e->failed.empty()) return fail(e, P2PG_ERR_STATE, "set_anti_entropy: " + e->failed);
+  if (period > 0 && !e->h_ttl.empty())
+    return fail(e, P2PG_ERR_STATE, "set_anti_entropy: not available together with hop limits (p2pg_set_ttl): a pulled "
+                                   "message's remaining budget is no function of the round");
+  if (period > 0 && e->pol_on)
+    return fail(e, P2PG_ERR_STATE, "set_anti_entropy: not available together with a relay policy (p2pg_set_relay_policy)");
+  if (period == 0) {  // the engine without this call
+    if (!e->ae.on()) return P2PG_OK;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    free_pull(e);
+    e->ae = anti_entropy::Setting{};
+    e->ae_seed = 0;
+    return P2PG_OK;
+  }
+  e->ae.first = first;
+  e->ae.last = last;
+  e->ae.period = period;
+  e->ae_seed = seed;
+  e->pull_round = -1;
+  e->pull_log.clear();
+  return P2PG_OK;
+}
+
+int32_t p2pg_pull_partner_slot(uint32_t round, uint32_t peer, uint32_t deg, uint64_t seed) {
+  if (deg == 0u) return -1;
+  return (int32_t)pull_partner_slot(round, peer, deg, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+int p2pg_get_pull_stats(p2pg_engine* e, int64_t cap, p2pg_pull_stats* out, int64_t* n_out) {
+  if (!e || cap < 0 || !n_out || (cap > 0 && !out)) return fail(e, P2PG_ERR_ARG, "get_pull_stats: bad arguments");
+  const int64_t n = (int64_t)e->pull_log.size();
+  for (int64_t i = 0; i < n && i < cap; ++i) out[i] = e->pull_log[i];
+  *n_out = n;
+  return P2PG_OK;
 }
 
 }  // extern "C"
@@ -1568,6 +1683,8 @@ int p2pg_reset(p2pg_engine* e) {
   e->tally_read_at = -1;
   e->exp_pending = e->exp_final = -1;  // (the hop limits themselves stay and are replayed)
   e->pol_pending = -1;                 // (and so does the relay policy)
+  e->pull_round = -1;                  // (and the anti-entropy setting; the run's records go)
+  e->pull_log.clear();
   e->round = 0;
   e->done = false;
   e->failed.clear();
@@ -1608,7 +1725,8 @@ bool split_round(const p2pg_engine* e) {
 // flight, or a scheduled start at or after the next round.
 bool close_round(p2pg_engine* e, const uint64_t* tot, int32_t push_form, bool pushed_e, bool rows_whole,
                  uint64_t lost, p2pg_round_stats* out) {
-  const bool active = tot[ST_NEW] != 0 || start_ahead(e, e->round + 1);
+  // (anti-entropy: a request round at or ahead, or an exchange in flight, keeps the run going)
+  const bool active = tot[ST_NEW] != 0 || start_ahead(e, e->round + 1) || e->ae.arrival_ahead((int64_t)e->round + 1);
   if (out) {
     out->round = e->round;
     out->active = active ? 1 : 0;
@@ -1721,9 +1839,21 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   // Peer downtime: somebody is offline in this round (round 0 has no receive pass, and an
   // origination at an offline peer is refused, so it has nothing to undo).
   facts.offline = e->down_on && e->round > 0 && e->down_sweep.offline_round(e->round);
+  // Anti-entropy: the replies of request round e->round - 2 arrive in this round.
+  const bool pull = e->ae.on() && e->ae.arrival_round(e->round);
+  facts.pull = pull;
   facts.skip_frontier = e->skip_frontier;
   const rp::RoundPlan plan = rp::plan_round(e->hist, e->rules, caps, facts);
   p.store_f = plan.store_f;
+  if (pull) {
+    // before the receive pass, while seen is the state at the end of the last round: the partner
+    // draws, the losses, and what each reply carries (relay_pull.hip)
+    if ((rc = ensure_pull(e))) return rc;
+    HIPCHK(e, hipMemsetAsync(e->d_pull_cnt, 0, PULL_BYTES, e->stream));
+    e->pull_round = e->round;
+    if ((rc = timed(e, 0, [&] { return launch_pull_gather(g, s, p, down(e), pull_of(e, e->round), e->stream); })))
+      return rc;
+  }
   uint64_t tot[STAT_N] = {0};
   // round 0's counters are the host's: origination stats from the host copy of the sources
   // (computed once per sources and graph)
@@ -1772,6 +1902,8 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   }
   if (facts.offline)  // the receipts the pass made at offline peers did not happen (relay_offline.hip)
     if ((rc = timed(e, 0, [&] { return launch_offline(g, s, p, down(e), e->stream); }))) return rc;
+  if (pull)  // what the replies carried and no relay copy delivered: first receipts of this round
+    if ((rc = timed(e, 0, [&] { return launch_pull_apply(g, s, p, pull_of(e, e->round), e->stream); }))) return rc;
   if (orig)  // Node.send_to_nodes at the origins of this round (node.py:106-112)
     if ((rc = timed(e, 0, [&] {
            return launch_originate(g, s, p, e->d_sched_peer, e->d_sched_msg, e->d_sched_grp, orig->g_lo,
@@ -1780,7 +1912,7 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
       return rc;
   if (s.hop)
     if ((rc = timed(e, 3, [&] {
-           return launch_record(graph_for_arrivals(e, e->round), s, p, e->stream);
+           return launch_record(graph_for_arrivals(e, e->round), s, p, pull_of(e, e->round), e->stream);
          })))
       return rc;
   auto read_stats = [&]() -> int {
@@ -1863,8 +1995,24 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     hipError_t x = enqueue_lost_count(e, g, graph_for_arrivals(e, e->round), e->round);
     if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("step (lost sends): ") + hipGetErrorString(x));
   }
+  if (pull)
+    HIPCHK(e, hipMemcpyAsync(e->h_pull_cnt, e->d_pull_cnt, PULL_BYTES, hipMemcpyDeviceToHost, e->stream));
   if ((rc = read_stats())) return rc;
   std::memcpy(e->stats_base, e->h_stats, sizeof(e->stats_base));  // the next round counts from here
+  if (pull) {  // the exchange is complete: its record (p2pg_get_pull_stats)
+    uint64_t c[PULL_N] = {0};
+    for (int sh = 0; sh < STAT_SHARDS; ++sh)
+      for (int i = 0; i < PULL_N; ++i) c[i] += e->h_pull_cnt[sh * PULL_N + i];
+    p2pg_pull_stats rec;
+    rec.request_round = e->round - 2;
+    rec.reserved = 0;
+    rec.requests = c[PL_REQUESTS];
+    rec.requests_lost = c[PL_REQUESTS_LOST];
+    rec.replies = c[PL_REPLIES];
+    rec.replies_lost = c[PL_REPLIES_LOST];
+    rec.repaired = c[PL_REPAIRED];
+    e->pull_log.push_back(rec);
+  }
   if ((rc = check_scatter_list(e, e->h_stats[STAT_COUNT]))) return rc;
   if (plan.held) {
     // the form of the held-back push, by the rule of the rounds that push at once (the density of
@@ -1918,6 +2066,7 @@ static bool decay_batchable(const p2pg_engine* e) {
   f.late_starts = e->last_start != 0;
   f.expiry_ahead = expiry_ahead(e, e->round);
   f.offline_ahead = e->down_on && e->down_sweep.offline_ahead(e->round);
+  f.pull_ahead = e->ae.arrival_ahead(e->round);
   f.frontier_needed = frontier_needed(e);
   f.autostop = !(e->cfg.flags & P2PG_FLAG_NO_AUTOSTOP);
   f.auto_buf = e->auto_buf != nullptr;
@@ -1952,7 +2101,7 @@ static int run_decay_batch(p2pg_engine* e, int32_t R, p2pg_round_stats* out, int
     if (i + 2 < n_left && partial_rows(e)) p.store_f = 2;
     partial[i] = p.store_f == 2;
     rc = timed(e, 4, [&] { return launch_gossip_update(g, s, p, e->stream); });
-    if (rc == P2PG_OK && s.hop) rc = timed(e, 3, [&] { return launch_record(g, s, p, e->stream); });
+    if (rc == P2PG_OK && s.hop) rc = timed(e, 3, [&] { return launch_record(g, s, p, pull_of(e, -1), e->stream); });
     p.dedup_push = rp::push_dedup(e->hist, e->rules);
     if (rc == P2PG_OK)
       rc = timed(e, 2, [&] {
@@ -2058,7 +2207,7 @@ int p2pg_get_new_deliveries(p2pg_engine* e, int64_t cap, int32_t* peer, int32_t*
   HIPCHK(e, hipMalloc((void**)&dpar, sizeof(int32_t) * c));
   HIPCHK(e, hipMalloc((void**)&dcnt, sizeof(unsigned long long)));
   HIPCHK(e, hipMemsetAsync(dcnt, 0, sizeof(unsigned long long), e->stream));
-  hipError_t lr = launch_deliveries(g, e->st, p, cap, dpeer, dmsg, dpar, dcnt, e->stream);
+  hipError_t lr = launch_deliveries(g, e->st, p, pull_of(e, p.round), cap, dpeer, dmsg, dpar, dcnt, e->stream);
   unsigned long long cnt = 0;
   if (lr == hipSuccess) lr = hipMemcpyAsync(&cnt, dcnt, sizeof(cnt), hipMemcpyDeviceToHost, e->stream);
   if (lr == hipSuccess) lr = hipStreamSynchronize(e->stream);
@@ -2137,7 +2286,7 @@ int p2pg_get_sends(p2pg_engine* e, int64_t cap, int32_t* sender, int32_t* receiv
   if (lr == hipSuccess) lr = hipMalloc((void**)&dl, c);
   if (lr == hipSuccess) lr = hipMemsetAsync(e->d_cnt2, 0, 2 * sizeof(unsigned long long), e->stream);
   if (lr == hipSuccess)
-    lr = launch_sends(graph(e), graph_for_arrivals(e, r), e->st, p, down(e), true, cap, ds, dr, dm, dl, e->d_cnt2, e->stream);
+    lr = launch_sends(graph(e), graph_for_arrivals(e, r), e->st, p, down(e), pull_of(e, r), true, cap, ds, dr, dm, dl, e->d_cnt2, e->stream);
   unsigned long long cnt = 0;
   if (lr == hipSuccess) lr = hipMemcpyAsync(&cnt, e->d_cnt2, sizeof(cnt), hipMemcpyDeviceToHost, e->stream);
   if (lr == hipSuccess) lr = hipStreamSynchronize(e->stream);
@@ -2177,6 +2326,8 @@ int p2pg_get_sends(p2pg_engine* e, int64_t cap, int32_t* sender, int32_t* receiv
 
 int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32_t* msg) {
   if (!e || n < 0 || (n > 0 && (!peer || !msg))) return fail(e, P2PG_ERR_ARG, "drop_relays: bad arguments");
+  if (e && e->ae.on())
+    return fail(e, P2PG_ERR_STATE, "drop_relays: not available while anti-entropy is set (p2pg_set_anti_entropy)");
   int rc = sends_state(e, "drop_relays");
   if (rc) return rc;
   if (tally_on(e) && e->tally_read_at == e->round)
@@ -2398,6 +2549,9 @@ int p2pg_set_global_ids(p2pg_engine* e, const int32_t* gid) {
   if (gid && e->down_on)
     return fail(e, P2PG_ERR_STATE, "set_global_ids: peer downtime (p2pg_set_downtime) is not available on a "
                                    "vertex-partitioned rank");
+  if (gid && e->ae.on())
+    return fail(e, P2PG_ERR_STATE, "set_global_ids: anti-entropy (p2pg_set_anti_entropy) is not available on a "
+                                   "vertex-partitioned rank");
   HIPCHK(e, hipSetDevice(e->cfg.device));
   dfree(e->d_gid);
   e->h_gid.clear();
@@ -2607,6 +2761,8 @@ int p2pg_update_edges(p2pg_engine* e, int64_t n_add, const int32_t* add, int64_t
     return fail(e, P2PG_ERR_ARG, "update_edges: bad arguments");
   if (e->d_gid || (e->cfg.flags & P2PG_FLAG_LOCAL_GRAPH))
     return fail(e, P2PG_ERR_STATE, "update_edges: not supported on a vertex-partitioned rank");
+  if (e->ae.on())
+    return fail(e, P2PG_ERR_STATE, "update_edges: not available while anti-entropy is set (p2pg_set_anti_entropy)");
   if (e->arr_round >= 0 && e->arr_round == e->round)
     return fail(e, P2PG_ERR_STATE, "update_edges: one update per round boundary");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "update_edges: a round has begun (step_begin)");
@@ -2866,6 +3022,8 @@ int p2pg_snapshot(p2pg_engine* e, void* buf, int64_t cap) {
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold a relay policy (p2pg_set_relay_policy)");
   if (e->down_on)
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold peer downtime (p2pg_set_downtime)");
+  if (e->ae.on())
+    return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold anti-entropy exchanges (p2pg_set_anti_entropy)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "snapshot: a round has begun (step_begin)");
   if (e->arr_round >= 0 && e->arr_round == e->round)
     return fail(e, P2PG_ERR_STATE, "snapshot: take it before a topology update or after the next round");
@@ -2938,6 +3096,8 @@ int p2pg_restore(p2pg_engine* e, const void* buf, int64_t size) {
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold a relay policy (p2pg_set_relay_policy)");
   if (e->down_on)
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold peer downtime (p2pg_set_downtime)");
+  if (e->ae.on())
+    return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold anti-entropy exchanges (p2pg_set_anti_entropy)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "restore: a round has begun (step_begin)");
   SnapHeader h;
   std::memcpy(&h, buf, sizeof(h));

@@ -10,6 +10,7 @@
 //   gossip  : key = (seed_lo, seed_hi),           ctr = (round, peer, msg_global, TAG_GSP | blk<<24)
 //   churn   : key = (seed_lo, seed_hi),           ctr = (round, min(a,b), max(a,b), TAG_CHN)
 //   policy  : key = (seed_lo, seed_hi),           ctr = (round, peer, msg_global, TAG_RLY)
+//   pull    : key = (seed_lo, seed_hi),           ctr = (round, peer, 0, TAG_AEP)
 #pragma once
 #include <stdint.h>
 
@@ -30,6 +31,7 @@ constexpr uint32_t TAG_SRC = 0x00535243u;  // 'SRC'
 constexpr uint32_t TAG_GSP = 0x00475350u;  // 'GSP'
 constexpr uint32_t TAG_CHN = 0x0043484Eu;  // 'CHN'
 constexpr uint32_t TAG_RLY = 0x00524C59u;  // 'RLY' relay policy
+constexpr uint32_t TAG_AEP = 0x00414550u;  // 'AEP' anti-entropy partner
 constexpr uint32_t TAG_RRG = 0x00525247u;  // 'RRG' random-regular generator
 constexpr uint32_t TAG_GNP = 0x00474E50u;  // 'GNP'
 constexpr uint32_t TAG_BAG = 0x00424147u;  // 'BAG' Barabasi-Albert generator
@@ -221,6 +223,14 @@ P2PG_HD bool relay_muted(uint32_t round, uint32_t peer, uint32_t msg, uint32_t t
   if (threshold == 0xFFFFFFFFu) return true;
   u32x4 c = {round, peer, msg, TAG_RLY};
   return philox4x32_10(c, seed_lo, seed_hi).x < threshold;
+}
+
+// Anti-entropy (p2pg_set_anti_entropy): the slot, in its ascending connection list of length
+// deg >= 1, of the connection `peer` sends its request of round `round` to.
+P2PG_HD uint32_t pull_partner_slot(uint32_t round, uint32_t peer, uint32_t deg, uint32_t seed_lo,
+                                   uint32_t seed_hi) {
+  u32x4 c = {round, peer, 0u, TAG_AEP};
+  return lemire32(philox4x32_10(c, seed_lo, seed_hi).x, deg);
 }
 
 }  // namespace p2pg

@@ -2158,15 +2158,20 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void k_gossip_fused(DevGraph g, D
 // Validation: the lowest-id neighbour v whose round-(r-1) send of message m reached u
 // (receivers process senders in ascending id -- the harness's stand-in for TCP arrival
 // order).  Returns -2 if none: the receipt is the message's own origination (its start round).
-__device__ int32_t find_parent(const DevGraph& g, const DevState& st, const RoundParams& p,
+// In an arrival round of an anti-entropy exchange (pl.R set) the reply is one more arriving packet:
+// if it carried m, u's partner of request round p.round - 2 is a sender too, and the result is the
+// lower of the two ids.
+__device__ int32_t find_parent(const DevGraph& g, const DevState& st, const RoundParams& p, const Pull& pl,
                                int64_t u, int m) {
   const int prv = (p.round & 1) ^ 1;
   const int W = st.W;
   const uint64_t bit = 1ull << (m & 63);
   const int w = m >> 6;
   const int64_t beg = g.rowptr[u], end = g.rowptr[u + 1];
+  const int32_t pp = (pull_word(st, pl, u, w) & bit) ? pull_partner(g, pl, p.round - 2, u) : -1;
   for (int64_t e = beg; e < end; ++e) {
     const int32_t v = g.colidx[e];
+    if (pp >= 0 && v >= pp) return pp;  // (the partner is a connection: the walk meets it)
     if (g.gone && g.gone[e]) continue;  // lost with its connection (topology update)
     if (!bit_test(st.A[prv], v)) continue;
     if (!(st.F[prv][(int64_t)v * W + w] & bit)) continue;
@@ -2198,10 +2203,10 @@ __device__ int32_t find_parent(const DevGraph& g, const DevState& st, const Roun
     }
     return v;
   }
-  return -2;
+  return pp >= 0 ? pp : -2;
 }
 
-__global__ __launch_bounds__(256) void k_record(DevGraph g, DevState st, RoundParams p) {
+__global__ __launch_bounds__(256) void k_record(DevGraph g, DevState st, RoundParams p, Pull pl) {
   const int lane = threadIdx.x & 63;
   const int wib = wave_in_block();
   const int cur = p.round & 1;
@@ -2223,7 +2228,7 @@ __global__ __launch_bounds__(256) void k_record(DevGraph g, DevState st, RoundPa
           f &= f - 1ull;
           const int m = w * 64 + bit;
           st.hop[u * st.M + m] = p.round;
-          const int32_t par = p.round == 0 ? -1 : find_parent(g, st, p, u, m);
+          const int32_t par = p.round == 0 ? -1 : find_parent(g, st, p, pl, u, m);
           st.parent[u * st.M + m] = par < 0 ? -1 : par;  // (no sender: an origination)
         }
       }
@@ -2231,7 +2236,7 @@ __global__ __launch_bounds__(256) void k_record(DevGraph g, DevState st, RoundPa
   }
 }
 
-__global__ __launch_bounds__(256) void k_deliveries(DevGraph g, DevState st, RoundParams p,
+__global__ __launch_bounds__(256) void k_deliveries(DevGraph g, DevState st, RoundParams p, Pull pl,
                                                     int64_t cap, int32_t* peer, int32_t* msg,
                                                     int32_t* parent,
                                                     unsigned long long* counter) {
@@ -2259,7 +2264,7 @@ __global__ __launch_bounds__(256) void k_deliveries(DevGraph g, DevState st, Rou
           if ((int64_t)pos < cap) {
             peer[pos] = (int32_t)u;
             msg[pos] = m;
-            const int32_t par = p.round == 0 ? -1 : find_parent(g, st, p, u, m);
+            const int32_t par = p.round == 0 ? -1 : find_parent(g, st, p, pl, u, m);
             parent[pos] = par < 0 ? -1 : par;  // (no sender: an origination)
           }
         }
@@ -2738,18 +2743,18 @@ hipError_t launch_clear_arrivals(const DevState& st, int32_t round, int64_t V, h
   return hipGetLastError();
 }
 
-hipError_t launch_record(const DevGraph& g, const DevState& st, const RoundParams& p,
+hipError_t launch_record(const DevGraph& g, const DevState& st, const RoundParams& p, const Pull& pl,
                          hipStream_t s) {
   const int grid = grid_tasks((g.V + 31) >> 5);
-  hipLaunchKernelGGL(k_record, dim3(grid), dim3(256), 0, s, g, st, p);
+  hipLaunchKernelGGL(k_record, dim3(grid), dim3(256), 0, s, g, st, p, pl);
   return hipGetLastError();
 }
 
-hipError_t launch_deliveries(const DevGraph& g, const DevState& st, const RoundParams& p,
+hipError_t launch_deliveries(const DevGraph& g, const DevState& st, const RoundParams& p, const Pull& pl,
                              int64_t cap, int32_t* peer, int32_t* msg, int32_t* parent,
                              unsigned long long* counter, hipStream_t s) {
   const int grid = grid_tasks((g.V + 31) >> 5);
-  hipLaunchKernelGGL(k_deliveries, dim3(grid), dim3(256), 0, s, g, st, p, cap, peer, msg,
+  hipLaunchKernelGGL(k_deliveries, dim3(grid), dim3(256), 0, s, g, st, p, pl, cap, peer, msg,
                      parent, counter);
   return hipGetLastError();
 }

@@ -17,8 +17,8 @@ namespace {
 // Did neighbour y's round-(r-1) send of this lane's word reach v?  (find_parent's test, word-wide:
 // y relayed in round r-1 -- its A bit and frontier word --, the connection was not removed
 // before the messages arrived, and churn did not drop it.)  Flood only; wave-uniform y.
-__device__ __forceinline__ uint64_t prev_sends(const DevGraph& gp, const DevState& st, const RoundParams& p,
-                                               int64_t v, int32_t y, int64_t slot, int w) {
+__device__ __forceinline__ uint64_t relay_sends(const DevGraph& gp, const DevState& st, const RoundParams& p,
+                                                int64_t v, int32_t y, int64_t slot, int w) {
   const int prv = (p.round & 1) ^ 1;
   if (gp.gone && gp.gone[slot]) return 0ull;
   if (!bit_test(st.A[prv], y)) return 0ull;
@@ -26,6 +26,14 @@ __device__ __forceinline__ uint64_t prev_sends(const DevGraph& gp, const DevStat
                                    p.cseed_lo, p.cseed_hi))
     return 0ull;
   return w < st.W ? st.F[prv][(int64_t)y * st.W + w] : 0ull;
+}
+
+// ... or, anti-entropy, did y's reply carry it?  partner = v's partner of the exchange whose
+// replies arrive in this round (-1: none arrived at v), pw = what the reply carried in this word.
+__device__ __forceinline__ uint64_t prev_sends(const DevGraph& gp, const DevState& st, const RoundParams& p,
+                                               int64_t v, int32_t y, int64_t slot, int w, int32_t partner,
+                                               uint64_t pw) {
+  return relay_sends(gp, st, p, v, y, slot, w) | (y == partner ? pw : 0ull);
 }
 
 // One wave per active peer v of round r = p.round (A[r&1]), lane = word of a 64-word slice.
@@ -40,7 +48,7 @@ __device__ __forceinline__ uint64_t prev_sends(const DevGraph& gp, const DevStat
 // peers without a lost connection are skipped.  cnt[0] = sends emitted.
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_sends(DevGraph gs, DevGraph gp, DevState st, RoundParams p,
-                                               Downtime d, int64_t cap, int32_t* __restrict__ snd,
+                                               Downtime d, Pull pl, int64_t cap, int32_t* __restrict__ snd,
                                                int32_t* __restrict__ rcv, int32_t* __restrict__ msg,
                                                uint8_t* __restrict__ lostf,
                                                unsigned long long* __restrict__ cnt) {
@@ -82,11 +90,14 @@ __global__ __launch_bounds__(256) void k_sends(DevGraph gs, DevGraph gp, DevStat
         if (last_lost < 0) continue;
         last_lost += 1;
       }
+      // anti-entropy: the partner whose reply arrived at v in this round is a sender too
+      const int32_t partner = pl.R && p.mode == 0 && bit_test(pl.PB, v) ? pull_partner(gp, pl, p.round - 2, v) : -1;
       for (int sl = 0; sl < nslices; ++sl) {
         const int w = sl * 64 + lane;
         const uint64_t f = w < W ? st.F[cur][v * W + w] : 0ull;
         if (!__ballot(f != 0ull)) continue;
         if (p.mode == 0) {
+          const uint64_t pw = partner >= 0 ? pull_word(st, pl, v, w) : 0ull;
           uint64_t rem = p.round > 0 ? f : 0ull;
           int64_t jp = gp.rowptr[v];
           const int64_t ep = gp.rowptr[v + 1];
@@ -96,7 +107,7 @@ __global__ __launch_bounds__(256) void k_sends(DevGraph gs, DevGraph gp, DevStat
             while (jp < ep) {
               const int32_t y = gp.colidx[jp];
               if (y > u) break;
-              const uint64_t sy = __ballot(rem != 0ull) ? prev_sends(gp, st, p, v, y, jp, w) : 0ull;
+              const uint64_t sy = __ballot(rem != 0ull) ? prev_sends(gp, st, p, v, y, jp, w, partner, pw) : 0ull;
               if (y == u) pu = rem & sy;
               rem &= ~sy;
               ++jp;
@@ -193,13 +204,13 @@ __global__ __launch_bounds__(256) void k_rebuild_aw(DevState st, int32_t round, 
 }  // namespace
 
 hipError_t launch_sends(const DevGraph& gs, const DevGraph& gp, const DevState& st, const RoundParams& p,
-                        const Downtime& d, bool emit, int64_t cap, int32_t* snd, int32_t* rcv, int32_t* msg, uint8_t* lost,
+                        const Downtime& d, const Pull& pl, bool emit, int64_t cap, int32_t* snd, int32_t* rcv, int32_t* msg, uint8_t* lost,
                         unsigned long long* cnt, hipStream_t s) {
   const int grid = grid_tasks((gs.V + 31) >> 5);
   if (emit)
-    hipLaunchKernelGGL(k_sends<true>, dim3(grid), dim3(256), 0, s, gs, gp, st, p, d, cap, snd, rcv, msg, lost, cnt);
+    hipLaunchKernelGGL(k_sends<true>, dim3(grid), dim3(256), 0, s, gs, gp, st, p, d, pl, cap, snd, rcv, msg, lost, cnt);
   else
-    hipLaunchKernelGGL(k_sends<false>, dim3(grid), dim3(256), 0, s, gs, gp, st, p, d, cap, snd, rcv, msg, lost, cnt);
+    hipLaunchKernelGGL(k_sends<false>, dim3(grid), dim3(256), 0, s, gs, gp, st, p, d, pl, cap, snd, rcv, msg, lost, cnt);
   return hipGetLastError();
 }
 

@@ -207,13 +207,14 @@ __device__ __forceinline__ int64_t find_slot(const DevGraph& gs, int64_t beg, in
 //   gp whose round-(r-1) send reached v (k_sends' walk: `rem` = bits whose sender is not found
 //   yet).  Only a neighbour that IS some bit's sender costs a second wave sum and takes its bits
 //   back off its own count (an add of -c: the counters are sums modulo 2^64, exact once the
-//   pass is done).
+//   pass is done).  In an arrival round of an anti-entropy exchange the partner whose reply arrived
+//   at v is a sender of the bits the reply carried (pl).
 // Gossip: deg <= k sends every bit to every connection (as flood, nobody excluded); else the
 //   Philox picks are re-drawn, lane-balanced over a list of the slice's receipts, and aggregated
 //   per connection in the wave's LDS table (rows of at most HUB_T connections), so the global
 //   atomics are one per connection that was picked; wider rows add per pick.
 __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, DevState st, RoundParams p,
-                                                    Downtime d,
+                                                    Downtime d, Pull pl,
                                                     unsigned long long* __restrict__ sent,
                                                     unsigned long long* __restrict__ received) {
   __shared__ uint32_t tab_all[WPB][HUB_T];
@@ -239,6 +240,8 @@ __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, De
       const bool picks = p.mode != 0 && (int)deg > p.fanout;
       const bool use_tab = picks && deg <= (uint32_t)HUB_T;
       unsigned long long v_sent = 0;  // wave-uniform
+      // anti-entropy: the partner whose reply arrived at v in this round is a sender too (k_sends)
+      const int32_t partner = pl.R && p.mode == 0 && bit_test(pl.PB, v) ? pull_partner(gp, pl, p.round - 2, v) : -1;
       if (use_tab) {
         for (uint32_t i = lane; i < deg; i += 64) tab[i] = 0u;
         wave_lds_sync();
@@ -261,10 +264,11 @@ __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, De
           if (p.mode == 0 && p.round > 0) {
             // ... but a bit's sender
             uint64_t rem = f;
+            const uint64_t pw = partner >= 0 ? pull_word(st, pl, v, w) : 0ull;
             const int64_t ep = gp.rowptr[v + 1];
             for (int64_t jp = gp.rowptr[v]; jp < ep && __ballot(rem != 0ull); ++jp) {
               const int32_t y = gp.colidx[jp];
-              const uint64_t sy = prev_sends(gp, st, p, v, y, jp, w);
+              const uint64_t sy = prev_sends(gp, st, p, v, y, jp, w) | (y == partner ? pw : 0ull);
               const uint64_t pu = rem & sy;
               rem &= ~sy;
               if (!__ballot(pu != 0ull)) continue;
@@ -368,8 +372,9 @@ hipError_t launch_column_count(const uint64_t* plane, const uint32_t* A, int64_t
 }
 
 hipError_t launch_peer_tally(const DevGraph& gs, const DevGraph& gp, const DevState& st, const RoundParams& p,
-                             const Downtime& d, unsigned long long* sent, unsigned long long* received, hipStream_t s) {
-  hipLaunchKernelGGL(k_peer_tally, dim3(grid_tasks((gs.V + 31) >> 5)), dim3(256), 0, s, gs, gp, st, p, d, sent,
+                             const Downtime& d, const Pull& pl, unsigned long long* sent,
+                             unsigned long long* received, hipStream_t s) {
+  hipLaunchKernelGGL(k_peer_tally, dim3(grid_tasks((gs.V + 31) >> 5)), dim3(256), 0, s, gs, gp, st, p, d, pl, sent,
                      received);
   return hipGetLastError();
 }

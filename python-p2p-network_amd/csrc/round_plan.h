@@ -83,6 +83,9 @@ struct RoundFacts {
   bool policy = false;         // a relay policy acts on it (every round > 0 of a policy engine)
   bool offline = false;        // somebody is offline in it (p2pg_set_downtime): the receipts its
                                // receive pass made at the offline peers are undone before its push
+  bool pull = false;           // the replies of an anti-entropy exchange arrive in it
+                               // (p2pg_set_anti_entropy): what they carried joins its first receipts
+                               // between the receive pass and the push
   bool skip_frontier = false;  // nobody observes its frontier rows (inside p2pg_run)
 };
 
@@ -174,12 +177,15 @@ inline bool push_dedup(const RoundHistory& h, const RoundRules& r) {
 // expiry round's then leaves by row atomics, a pure policy round's in the form its own density
 // chose.  An offline round (peer downtime) is special in the same way -- its rows are rewritten
 // between the receive pass and the push (relay_offline.hip) -- but not held: the undo is done
-// before the push, which leaves in the round, in the form the density rule gives.  The rounds
-// around a special round keep every form they have.
+// before the push, which leaves in the round, in the form the density rule gives.  The arrival
+// round of an anti-entropy exchange is planned like an offline round: k_pull_apply (relay_pull.hip)
+// ORs the pulled receipts into the rows before the push, so whole rows, unfused, never blind, not
+// held; request and reply rounds launch nothing and are no special rounds.  The rounds around a
+// special round keep every form they have.
 inline RoundPlan plan_round(const RoundHistory& h, const RoundRules& r, const RoundCaps& c,
                             const RoundFacts& f) {
   RoundPlan p;
-  const bool special = f.origination || f.expiry || f.policy || f.offline;
+  const bool special = f.origination || f.expiry || f.policy || f.offline || f.pull;
   // the update / pull-only pass of this round (fused and update+push rounds set their own): a
   // frontier nobody observes is written by its nonzero words only
   if (c.gossip && !special && f.skip_frontier && c.partial_rows) p.store_f = 2;
@@ -249,6 +255,8 @@ struct DecayFacts {
   bool expiry_ahead = false;     // a hop limit expires from here on: its round runs its own schedule
   bool offline_ahead = false;    // somebody is offline in a round from here on (p2pg_set_downtime):
                                  // that round runs its own schedule
+  bool pull_ahead = false;       // the replies of an anti-entropy exchange arrive in a round from here
+                                 // on (p2pg_set_anti_entropy): that round runs its own schedule
   bool frontier_needed = false;  // every round's frontier rows are read whole (lost count, tallies,
                                  // relay policy)
   bool autostop = true;
@@ -260,7 +268,7 @@ inline bool decay_batchable(const RoundHistory& h, const RoundRules& r, const Ro
                             const DecayFacts& f) {
   return f.round > 0 && !f.frontier_needed && c.gossip && h.saw_dense && !h.last_push_e &&
          h.last_new < h.prev2_new && h.prev_sw > 0 && !f.consume_next && !f.arr_pending &&
-         !f.late_starts && !f.expiry_ahead && !f.offline_ahead && !c.partitioned && f.autostop && r.push_mode != 2 &&
+         !f.late_starts && !f.expiry_ahead && !f.offline_ahead && !f.pull_ahead && !c.partitioned && f.autostop && r.push_mode != 2 &&
          !f.auto_buf && c.sparse_scatter &&
          h.last_new * 16 < (uint64_t)f.V;  // the tail: small rounds, where the syncs dominate
 }

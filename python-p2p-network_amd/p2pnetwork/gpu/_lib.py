@@ -67,6 +67,18 @@ class RoundStatsC(ctypes.Structure):
     ]
 
 
+class PullStatsC(ctypes.Structure):
+    _fields_ = [
+        ("request_round", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("requests", ctypes.c_uint64),
+        ("requests_lost", ctypes.c_uint64),
+        ("replies", ctypes.c_uint64),
+        ("replies_lost", ctypes.c_uint64),
+        ("repaired", ctypes.c_uint64),
+    ]
+
+
 # every symbol declared in include/p2pgpu.h, with (restype, argtypes)
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -86,6 +98,7 @@ SIGNATURES = {
     "p2pg_churn_lost": (ctypes.c_int, [_U32, _U32, _U32, _U32, _U64]),
     "p2pg_relay_muted": (ctypes.c_int, [_U32, _U32, _U32, _U32, _U64]),
     "p2pg_peer_offline": (ctypes.c_int, [_I32, _I32, _I32]),
+    "p2pg_pull_partner_slot": (_I32, [_U32, _U32, _U32, _U64]),
     "p2pg_create": (ctypes.c_int, [ctypes.POINTER(Config), _PP]),
     "p2pg_load_csr": (ctypes.c_int, [_P, _I64, _P, _P]),
     "p2pg_set_sources": (ctypes.c_int, [_P, _I32, _P]),
@@ -94,6 +107,8 @@ SIGNATURES = {
     "p2pg_set_ttl": (ctypes.c_int, [_P, _I32, _P]),
     "p2pg_set_relay_policy": (ctypes.c_int, [_P, _I64, _P, _U64]),
     "p2pg_set_downtime": (ctypes.c_int, [_P, _I64, _P, _P]),
+    "p2pg_set_anti_entropy": (ctypes.c_int, [_P, _I32, _I32, _I32, _U64]),
+    "p2pg_get_pull_stats": (ctypes.c_int, [_P, _I64, _P, ctypes.POINTER(_I64)]),
     "p2pg_reset": (ctypes.c_int, [_P]),
     "p2pg_step": (ctypes.c_int, [_P, ctypes.POINTER(RoundStatsC)]),
     "p2pg_run": (ctypes.c_int, [_P, _I32, _P, ctypes.POINTER(_I32)]),

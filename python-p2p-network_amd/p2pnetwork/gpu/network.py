@@ -112,6 +112,11 @@ _SNAP_TOTAL_RELAYS_WORD = 13
 # p2pg_set_downtime: until = INT32_MAX, a peer that never returns
 _FOREVER = 0x7FFFFFFF
 
+# one anti-entropy exchange (p2pg_pull_stats)
+PULL_STATS_DTYPE = np.dtype([("request_round", np.int32), ("reserved", np.int32), ("requests", np.uint64),
+                             ("requests_lost", np.uint64), ("replies", np.uint64), ("replies_lost", np.uint64),
+                             ("repaired", np.uint64)])
+
 
 def churn_threshold(p_drop):
     """floor(p_drop * 2^32), the integer threshold of the per-round edge-drop mask."""
@@ -169,6 +174,7 @@ class GraphNetwork:
         self.relay_seed = 0
         self.offline_from = None     # int32 [V]: the peers' downtime intervals [from, until)
         self.offline_until = None    # (None = no downtime; until 0x7FFFFFFF = forever)
+        self.anti_entropy = None     # (period, first_round, last_round, seed), None = not set
         self._autostop = bool(autostop)
         self._next_round = 0         # the next round the engine runs
         self._quiet = False          # the engine went quiet (further steps run no round)
@@ -346,6 +352,52 @@ class GraphNetwork:
         on = bool((f >= 0).any())
         self.offline_from = f if on else None
         self.offline_until = u if on else None
+
+    def set_anti_entropy(self, period, first_round=0, last_round=None, seed=0):
+        """Periodic pull repair, before round 0 runs (or after ``reset``): in every round r with
+        ``first_round <= r <= last_round`` and ``(r - first_round) % period == 0`` each online peer
+        with a connection asks one drawn connection (``pull_partner``) for the messages it is
+        missing; the partner answers in round r + 1 and what the reply lists is first-received in
+        round r + 2 and relayed like any other receipt.  Requests and replies are lost like any
+        send of their round (churn, an offline receiver) and are counted per exchange
+        (``pull_stats``), never in the relay counters.  ``last_round`` is mandatory: the run goes on
+        until the last exchange is complete.  Not together with hop limits or a relay policy.
+        ``set_anti_entropy(None)`` removes it.  ``reset`` and ``broadcast`` keep it
+        (p2pg_set_anti_entropy)."""
+        if period is None or int(period) == 0:
+            self._check(_lib.lib().p2pg_set_anti_entropy(self._h, 0, 0, 0, 0))
+            self.anti_entropy = None
+            return
+        if last_round is None:
+            raise ValueError("set_anti_entropy needs last_round (the run ends after the last exchange)")
+        for x in (period, first_round, last_round):
+            if not -(1 << 31) <= int(x) <= _FOREVER:
+                raise ValueError("period, first_round and last_round must be int32")
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._check(_lib.lib().p2pg_set_anti_entropy(self._h, int(first_round), int(last_round), int(period), seed))
+        self.anti_entropy = (int(period), int(first_round), int(last_round), seed)
+        self._quiet = False
+
+    def pull_partner(self, round, peer):
+        """The connection ``peer`` sends its anti-entropy request of ``round`` to (whether or not
+        ``round`` is a request round), or -1 for a peer without connections
+        (p2pg_pull_partner_slot)."""
+        if self.anti_entropy is None:
+            raise ValueError("no anti-entropy is set")
+        nb = self.graph.neighbours(int(peer))
+        j = _lib.lib().p2pg_pull_partner_slot(int(round), int(peer), len(nb), self.anti_entropy[3])
+        return -1 if j < 0 else int(nb[j])
+
+    def pull_stats(self):
+        """The anti-entropy exchanges completed in this run, one record each (PULL_STATS_DTYPE:
+        request_round, requests, requests_lost, replies, replies_lost, repaired), in order of
+        request round (p2pg_get_pull_stats)."""
+        n = ctypes.c_int64()
+        self._check(_lib.lib().p2pg_get_pull_stats(self._h, 0, None, ctypes.byref(n)))
+        out = np.zeros(n.value, dtype=PULL_STATS_DTYPE)
+        if n.value:
+            self._check(_lib.lib().p2pg_get_pull_stats(self._h, n.value, _lib.ptr(out), ctypes.byref(n)))
+        return out
 
     def originate(self, msgs, peers, round=None):
         """Between rounds: start the unscheduled broadcasts ``msgs`` at ``peers`` in ``round``
