@@ -1162,7 +1162,10 @@ __device__ __forceinline__ void tbl_clear(ScatterLds& L, int j, int w) {
 // PART (vertex-partitioned gossip ranks, STORE_E): a receiver slot marked REV_GHOST is a ghost's
 // connection -- the mask goes into the ghost's row push (next[r+1] row + T bit, exchanged after the
 // round) as in a sparse round, every other one into its E slot.
-template <bool CHURN, int K, bool STORE_E, int PH = 0, bool PART = false, bool DIRECT = false, class CT>
+// PACKED: the caller knows that E rows are packed (st.AW[cur] is set), so the plane pointer is not
+// read from the kernel arguments per source for that test.
+template <bool CHURN, int K, bool STORE_E, int PH = 0, bool PART = false, bool DIRECT = false,
+          bool PACKED = false, class CT>
 __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& st,
                                             const RoundParams& p, ScatterLds& L, int lane,
                                             int64_t v, int64_t rb, int64_t deg, int chunk,
@@ -1246,7 +1249,7 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
   // The picks touch only the active words' table columns, so only those are cleared.
   const int nf = __popcll(fam);
   const bool compact = !CHURN && anyf && nf <= 32 &&
-                       (STORE_E ? st.AW[cur] != nullptr : g.gone == nullptr);
+                       (STORE_E ? PACKED || st.AW[cur] != nullptr : g.gone == nullptr);
   const bool use_tbl = anyf && !all;
   int seg = 64, rk_lane = 0, wc = 0, gl = 0;
   bool rk = false;
@@ -1394,7 +1397,7 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
       }
       // receiver-major: the row lands in the RECEIVER's slot for this connection, so the
       // pull streams its own contiguous slot range; packed: only the active words, in order
-      if (st.AW[cur]) {
+      if (PACKED || st.AW[cur]) {
         if (f) st_row(at_row(Eo, nj, W) + __popcll(fam & ((1ull << lane) - 1ull)), dropped ? 0ull : x);
       } else if (valid) {
         st_row(at_row(Eo, nj, W) + w, dropped ? 0ull : x);
@@ -1710,6 +1713,19 @@ constexpr int FG = 8;
 // 1.3-1.4 ms per c4 step faster on two boxes (2: no better; W = 32 / 16 shares equal,
 // profiles/r04/ab_fused_waves.txt)
 constexpr int FUSED_WAVES = 3;
+// A/B switches of the fused kernel's scalar state (profiles/fused_scalars; 0 = the form before):
+// P2PG_FS_MASKS: no wave-constant lane mask (lane < W, the store_f forms) is kept in SGPR pairs;
+// P2PG_FS_KARG: the per-peer kernel-argument reads come from registers;
+// P2PG_FS_GATHER: the gather slot loop works from the row's base address, not from q.beg per slot.
+#ifndef P2PG_FS_MASKS
+#define P2PG_FS_MASKS 1
+#endif
+#ifndef P2PG_FS_KARG
+#define P2PG_FS_KARG 1
+#endif
+#ifndef P2PG_FS_GATHER
+#define P2PG_FS_GATHER 1
+#endif
 // MODE 0: the fused dense round above.
 // MODE 1, PO (push only): the first dense round after an update (16 < W <= 64, packed E) -- the
 // peers are the round's active non-hub peers, their arrivals are their own frontier rows F[r&1]
@@ -1753,6 +1769,34 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void k_gossip_fused(DevGraph g, D
   const int64_t ntasks = (V + 31) >> 5;
   const bool valid = lane < W;
   const uint64_t fm = valid ? full_mask(lane, W, st.M) : 0ull;
+#if P2PG_FS_MASKS
+  // The wave-constant lane masks (lane < W; the frontier store's condition) would each live in an
+  // SGPR pair, spilled and read back at every use.  Instead: W in a VGPR, so `lane < W` is one
+  // compare of two vector registers where it is needed (row_lane(): an empty asm keeps the
+  // compiler from hoisting it out of the peer loop into a mask again), and the frontier store's
+  // form as one wave-uniform word.  (This, and AWc below, lean on how today's compiler allocates
+  // registers; no test sees it if that changes.  After a toolchain update re-run
+  // tools/isa_hot_path.py and compare with profiles/fused_scalars/hot_path_change.txt.)
+  int vW = W;
+  asm("" : "+v"(vW));
+  auto row_lane = [&]() {
+    int l = lane;
+    asm volatile("" : "+v"(l));
+    return l < vW;
+  };
+  const int store_form = p.store_f;  // 0 none, 1 whole rows, 2 nonzero words
+#else
+  auto row_lane = [&]() { return valid; };
+#endif
+#if P2PG_FS_KARG
+  // st.AW[cur], read per active peer: in a VGPR pair (the same value in every lane), so the
+  // store address is one vector multiply-add and neither the kernel-argument pointer nor the
+  // plane pointer is read back from a spill lane
+  // (not on partitioned ranks: the two registers take the generic-fanout W <= 32 instance there from
+  // 128 to 130 VGPRs, 4 -> 3 waves per SIMD, and the pull-only one from 6 to 5)
+  uint64_t* AWc = st.AW[cur];
+  if constexpr (!PART) asm("" : "+v"(AWc));
+#endif
   // per-lane counters are 32-bit and per task (<= 32 peers, none a hub: no overflow), folded
   // into wave-uniform 64-bit totals after each task (fewer live VGPRs than 64-bit lanes)
   // wave totals in 32 bits (8 fewer scalar registers): balanced_grid never gives a wave more
@@ -1820,8 +1864,8 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void k_gossip_fused(DevGraph g, D
     if (q.u < 0) return;
     // PO: the peer's frontier row (its new receipts of this round) instead of its seen row;
     // UP: the seen row and, in the stage's mask field, the push row (the arrivals)
-    if (valid) q.s = at_row(PO ? Fc : st.seen, q.u, W)[lane];
-    if (UP) q.am = valid ? at_row(st.next[cur], q.u, W)[lane] : 0ull;
+    if (row_lane()) q.s = at_row(PO ? Fc : st.seen, q.u, W)[lane];
+    if (UP) q.am = row_lane() ? at_row(st.next[cur], q.u, W)[lane] : 0ull;
     // PO: the row's active-word mask (a frontier row written by the update may hold stale words
     // outside it, RoundParams::store_f == 2)
     if (PO) q.am = ldc(st.AW[cur] + q.u);
@@ -1890,6 +1934,15 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void k_gossip_fused(DevGraph g, D
     // (a slot past the last active one keeps am = 0: its load mask is empty, no select needed)
     uint32_t sv[FG];
     uint64_t am[FG];
+#if P2PG_FS_GATHER
+    // slots relative to the row's first one, whose E row address is formed once: q.beg is a
+    // spilled scalar by now, and beg + idx read it back from its lane for every slot
+    const uint64_t* __restrict__ Sq = at_row(Src, q.beg, W);
+    const uint32_t sb = 0u;
+#else
+    const uint64_t* __restrict__ Sq = Src;
+    const uint32_t sb = q.beg;
+#endif
 #pragma unroll
     for (int k = 0; k < FG; ++k) {
       sv[k] = 0u;
@@ -1897,12 +1950,12 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void k_gossip_fused(DevGraph g, D
       if (m) {
         const int idx = __builtin_ctzll(m);
         m &= ~(1ull << idx);
-        sv[k] = q.beg + (uint32_t)idx;  // receiver-major E: the row of slot j is j
+        sv[k] = sb + (uint32_t)idx;  // receiver-major E: the row of slot j is j
         am[k] = (uint64_t)readlane64((int64_t)q.am, idx);
       }
     }
 #pragma unroll
-    for (int k = 0; k < FG; ++k) X[k] = src_word_m(Src, sv[k], W, am[k], am[k] & needm);
+    for (int k = 0; k < FG; ++k) X[k] = src_word_m(Sq, sv[k], W, am[k], am[k] & needm);
     mr = m;
   };
 
@@ -1952,8 +2005,8 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void k_gossip_fused(DevGraph g, D
   uint32_t prcv = 0;  // its receiver slots
   auto flush_pending = [&]() {
     if (pend) {
-      scatter_row<CHURN, K, true, 2, PART>(g, st, p, lds[wib], lane, pu, pbeg, pdeg, 0, 0, pnw, prcv,
-                                     0, c PROF_PASS);
+      scatter_row<CHURN, K, true, 2, PART, false, P2PG_FS_KARG != 0>(g, st, p, lds[wib], lane, pu, pbeg, pdeg,
+                                                                     0, 0, pnw, prcv, 0, c PROF_PASS);
       pend = false;
     }
   };
@@ -1983,7 +2036,7 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void k_gossip_fused(DevGraph g, D
     // PART: the rows other ranks pushed to u in the last round (exchanged; T bit), loaded now so
     // the wait below covers them
     uint64_t remote = 0;
-    if (PART && GATHER && ((ldc(st.T[cur] + (u >> 5)) >> (u & 31)) & 1u) && valid)
+    if (PART && GATHER && ((ldc(st.T[cur] + (u >> 5)) >> (u & 31)) & 1u) && row_lane())
       remote = at_row(st.next[cur], u, W)[lane];
     PROF_MARK(0);
     if (GATHER) {
@@ -2086,10 +2139,21 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void k_gossip_fused(DevGraph g, D
     }
     if (wm) {
       if (!PO) {
+#if P2PG_FS_MASKS
+        // (nw is zero outside the row: fm is, so form 2 needs no lane test)
+        if (store_form) {
+          if (store_form == 2 ? nw != 0ull : row_lane()) st_row(at_row(Fc, u, W) + lane, nw);
+        }
+#else
         if (valid && p.store_f && (p.store_f != 2 || nw)) st_row(at_row(Fc, u, W) + lane, nw);
+#endif
         aw |= 1u << (u & 31);
         if (lane == 0) {
+#if P2PG_FS_KARG
+          AWc[u] = wm;
+#else
           st.AW[cur][u] = wm;
+#endif
           c[ST_ACTIVE_W] += 1u << 16;  // ST_ACTIVE_V, packed (see finish_task)
           c[ST_DEG_ACT] += (uint32_t)deg;
         }
@@ -2102,8 +2166,8 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void k_gossip_fused(DevGraph g, D
       if (PL) {
         // (no pushes: the sparse push that follows reads the frontier row)
       } else if (__builtin_expect(deg <= (uint64_t)GCHUNK, 1)) {  // (94 % of the peers)
-        scatter_row<CHURN, K, true, 1, PART, PO || UP>(g, st, p, lds[wib], lane, u, a.beg, (int64_t)deg, 0, 0,
-                                       nw, a.rv, 0, c PROF_PASS);
+        scatter_row<CHURN, K, true, 1, PART, PO || UP, P2PG_FS_KARG != 0>(
+            g, st, p, lds[wib], lane, u, a.beg, (int64_t)deg, 0, 0, nw, a.rv, 0, c PROF_PASS);
         pend = true;
         pu = u;
         pbeg = a.beg;
@@ -2116,21 +2180,26 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void k_gossip_fused(DevGraph g, D
         scatter_wide<K>(g, st, p, lds[wib], lane, u, a.beg, (uint32_t)deg, nw, a.rv, c PROF_PASS);
       } else if (deg <= 64) {
         for (int ch = 0; (int64_t)ch * GCHUNK < (int64_t)deg; ++ch)
-          scatter_row<CHURN, K, true, 0, PART, PO || UP>(g, st, p, lds[wib], lane, u, a.beg, (int64_t)deg, ch, 0,
-                                      nw, a.rv, ch * GCHUNK, c PROF_PASS);
+          scatter_row<CHURN, K, true, 0, PART, PO || UP, P2PG_FS_KARG != 0>(
+              g, st, p, lds[wib], lane, u, a.beg, (int64_t)deg, ch, 0, nw, a.rv, ch * GCHUNK, c PROF_PASS);
       } else {
         for (int ch = 0; (int64_t)ch * GCHUNK < (int64_t)deg; ++ch) {
           const int off = (ch * GCHUNK) & 63;
           const uint32_t j = a.beg + (uint32_t)(ch * GCHUNK - off) + lane;
           const uint32_t rvb = j < a.end ? g.rev[j] : 0u;
           __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-          scatter_row<CHURN, K, true, 0, PART, PO || UP>(g, st, p, lds[wib], lane, u, a.beg, (int64_t)deg, ch, 0,
-                                      nw, rvb, off, c PROF_PASS);
+          scatter_row<CHURN, K, true, 0, PART, PO || UP, P2PG_FS_KARG != 0>(
+              g, st, p, lds[wib], lane, u, a.beg, (int64_t)deg, ch, 0, nw, rvb, off, c PROF_PASS);
         }
       }
     }
     PROF_MARK(3);
+#if P2PG_FS_MASKS
+    // (outside the row fm, the seen word and nw are all zero: no lane test)
+    if (!PO && !__ballot((a.s | nw) != fm)) nsat |= 1u << (u & 31);
+#else
     if (!PO && !__ballot(valid && (a.s | nw) != fm)) nsat |= 1u << (u & 31);
+#endif
   };
   for (;;) {
     if (sA.u < 0) break;
@@ -2507,6 +2576,12 @@ static void fused_launch(const DevGraph& g, const DevState& st, const RoundParam
   hipLaunchKernelGGL(kernel, dim3(balanced_grid(kernel, (g.V + 31) >> 5)), dim3(256), 0, s, g, st, p);
 }
 
+// The kernel takes packed E rows in the round's plane for granted (P2PG_FS_KARG: it does not test
+// st.AW[cur] per peer); every launcher below checks it before the first launch.
+static bool fused_planes_ok(const DevState& st) {
+  return st.AW[0] != nullptr && st.AW[1] != nullptr;
+}
+
 // ... by width: rows of W <= 32 words gather two slots per load (HALF)
 template <bool CH, int K, int MODE, bool PART = false>
 static void fused_launch_w(const DevGraph& g, const DevState& st, const RoundParams& p, hipStream_t s) {
@@ -2520,7 +2595,7 @@ static void fused_launch_w(const DevGraph& g, const DevState& st, const RoundPar
 // goes through the fused pipeline, whose wide-row chunks handle any degree).
 static bool part_launch_ok(const DevGraph& g, const DevState& st, int prv) {
   return g.gid != nullptr && g.rev != nullptr && st.W > GROUPED_W_MAX && st.W <= 64 &&
-         st.AW[prv] != nullptr && st.E[0] != st.E[1];
+         fused_planes_ok(st) && st.E[0] != st.E[1];
 }
 
 static hipError_t launch_gossip_fused_part(const DevGraph& g, const DevState& st,
@@ -2547,7 +2622,7 @@ hipError_t launch_gossip_pull(const DevGraph& g, const DevState& st, const Round
   }
   // packed rows (8 < W <= 64): the pull-only mode of the fused kernel (its pipeline crosses task
   // boundaries; W <= 32: two slots per gather load)
-  if (st.W <= 64 && st.AW[(p.round & 1) ^ 1] && p.phase < 0) {
+  if (st.W <= 64 && fused_planes_ok(st) && p.phase < 0) {
     RoundParams pp = p;
     // the sparse push of this round reads the frontier rows (its listed words only: whole rows,
     // or the nonzero words when nobody else can observe them, store_f == 2)
@@ -2661,7 +2736,7 @@ hipError_t launch_gossip_scatter(const DevGraph& g, const DevState& st, const Ro
   // switch it between engines of one process)
   const char* pf_env = std::getenv("P2PG_PUSH_FUSED");
   const bool push_fused = !(pf_env && std::strcmp(pf_env, "0") == 0);
-  if (store_e && push_fused && st.W <= 64 && st.AW[p.round & 1] != nullptr && hubs_ok && !g.gid) {
+  if (store_e && push_fused && st.W <= 64 && fused_planes_ok(st) && hubs_ok && !g.gid) {
     dispatch_fanout_churn(p, [&](auto ch, auto k) {
       fused_launch<decltype(ch)::value, decltype(k)::value, 1>(g, st, p, s);
     });
@@ -2678,7 +2753,7 @@ hipError_t launch_gossip_scatter(const DevGraph& g, const DevState& st, const Ro
 
 bool gossip_update_push_supported(const DevState& st) {
   return st.W > 16 && st.W > GROUPED_W_MAX && st.W <= 64 && st.AW[0] != nullptr &&
-         st.E[0] != nullptr;
+         st.AW[1] != nullptr && st.E[0] != nullptr;
 }
 
 hipError_t launch_gossip_update_push(const DevGraph& g, const DevState& st, const RoundParams& p,
@@ -2708,7 +2783,7 @@ hipError_t launch_gossip_update_push(const DevGraph& g, const DevState& st, cons
 
 bool gossip_fused_supported(const DevState& st) {
   if (st.W > 64 || st.E[0] == st.E[1]) return false;
-  return st.W <= GROUPED_W_MAX || st.AW[0] != nullptr;
+  return st.W <= GROUPED_W_MAX || (st.AW[0] != nullptr && st.AW[1] != nullptr);
 }
 
 hipError_t launch_gossip_fused(const DevGraph& g, const DevState& st, const RoundParams& p,
