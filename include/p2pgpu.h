@@ -37,7 +37,10 @@
  *                                    hops of the node_message events that put it there
  *   p2pg_peer_counters            <- per peer: Node.message_count_send / message_count_recv
  *                                    (node.py:65-67, :116; nodeconnection.py:215)
- *   p2pg_last_error              <- (reference swallows errors via debug_print, node.py:80-83)
+ *   p2pg_message_cost             <- per payload id: the send_to_node calls that carried it
+ *                                    (node.py:116) and the packets of it that a receive loop
+ *                                    handed on (nodeconnection.py:215)
+ *   p2pg_last_error             <- (reference swallows errors via debug_print, node.py:80-83)
  *
  * Conventions: plain C types only; 0 = OK, negative = error (message via p2pg_last_error);
  * no exceptions cross the ABI; the engine owns all device memory; caller keeps ownership of
@@ -93,6 +96,15 @@ extern "C" {
                                     frontier rows, a column count follows each round and a per-peer
                                     pass precedes the next (the price: DESIGN.md 4g).  Not on a
                                     vertex-partitioned rank, not with snapshots                  */
+
+#define P2PG_FLAG_MSG_COST 64u /* per-broadcast cost on the device: the send_to_node calls that
+                                    carried message m and those of them that arrived
+                                    (p2pg_message_cost).  Independent of P2PG_FLAG_TALLY (either,
+                                    both or neither).  M 16 bytes of device memory and 512 KB of
+                                    shard scratch per 4096 messages; every round keeps its whole frontier
+                                    rows and a per-message pass over its sends precedes the next
+                                    round (the price: DESIGN.md 4g).  Not on a vertex-partitioned
+                                    rank, not with snapshots                                     */
 
 typedef struct p2pg_engine p2pg_engine;
 typedef struct p2pg_graph p2pg_graph;
@@ -228,7 +240,8 @@ int p2pg_originate(p2pg_engine* e, int64_t n, const int32_t* msg, const int32_t*
  * round has run; while a finite limit is set p2pg_snapshot / p2pg_restore return P2PG_ERR_STATE.
  * A rejected call changes nothing.
  * An expiry round's sends become final at the start of the next round or inside p2pg_get_sends,
- * p2pg_peer_counters, p2pg_update_edges or p2pg_drop_relays, whichever comes first: read the
+ * p2pg_peer_counters, p2pg_message_cost, p2pg_update_edges or p2pg_drop_relays, whichever comes
+ * first: read the
  * round's deliveries before those (as for p2pg_drop_relays) -- they hold all its receipts, the
  * expired messages' last ones included; afterwards p2pg_get_new_deliveries for that round returns
  * P2PG_ERR_STATE, never a shortened list.  p2pg_drop_relays of an expired receipt is legal and
@@ -256,8 +269,8 @@ int p2pg_set_ttl(p2pg_engine* e, int32_t M, const int32_t* ttl);
  * round has run; while a policy is set p2pg_snapshot / p2pg_restore return P2PG_ERR_STATE.  A
  * rejected call changes nothing.
  * With a policy every round after round 0 is scheduled like an expiry round: the unfused
- * schedule, and its sends become final at the points named for p2pg_set_ttl (read the round's
- * deliveries first; p2pg_drop_relays of a muted receipt is legal and cancels nothing).  Its
+ * schedule, and its sends become final at the points named for p2pg_set_ttl (p2pg_message_cost among
+ * them; read the round's deliveries first; p2pg_drop_relays of a muted receipt is legal and cancels nothing).  Its
  * scatter_words is 0, the following round's touched_words counts what the held-back push
  * touched, and push_form reports the form chosen for that push from the round's own density
  * (P2PG_PUSH_ATOMIC or P2PG_PUSH_EDGE; P2PG_PUSH_ATOMIC in a round that is an expiry round too). */
@@ -419,6 +432,26 @@ int p2pg_message_tally(p2pg_engine* e, uint64_t* reach, uint64_t* hop_sum, int32
  * the same round boundary is refused (P2PG_ERR_STATE): read the counters after the changes of
  * a boundary.  p2pg_reset and p2pg_set_sources zero all tallies. */
 int p2pg_peer_counters(p2pg_engine* e, uint64_t* sent, uint64_t* received);
+/* With P2PG_FLAG_MSG_COST: what each broadcast cost, sent[M], received[M] (either may be NULL).
+ *   sent[m]     send_to_node calls that carried message m in the rounds run so far -- its first
+ *               receipts' relays and its originations -- lost ones included (node.py:116 counts
+ *               before sending), less relays withdrawn by p2pg_drop_relays.
+ *   received[m] those of them that are not lost: to churn, to a connection p2pg_update_edges
+ *               removed while the packet was in flight, or to a receiver that is offline in the
+ *               arrival round (nodeconnection.py:215 per payload id).
+ * These are the records of p2pg_get_sends binned by msg.  Pull packets of anti-entropy are not
+ * counted; the relays of pulled first receipts are.  On every run sum_m sent[m] = the sum of
+ * round_stats.relays, and with P2PG_FLAG_TALLY as well sum_m sent[m] = sum_v of
+ * p2pg_peer_counters' sent[v], likewise received.  sent[m] / (reach[m] - 1) - 1 is the relative
+ * message redundancy of broadcast m.
+ * The lifecycle is that of p2pg_peer_counters: a round's sends are counted once they are final --
+ * when the next round starts, inside p2pg_update_edges, or by this call, which first makes a
+ * held-back expiry / policy round final as p2pg_peer_counters does -- after which a
+ * p2pg_drop_relays or p2pg_update_edges at the same round boundary is refused (P2PG_ERR_STATE):
+ * read the counters after the changes of a boundary.  p2pg_reset and p2pg_set_sources[_at] zero
+ * the counters.  P2PG_ERR_STATE without the flag, before sources are set, between
+ * p2pg_step_begin and p2pg_step_end, and on a vertex-partitioned rank.                       */
+int p2pg_message_cost(p2pg_engine* e, uint64_t* sent, uint64_t* received);
 /* Summed device time per kernel class since the last reset (needs P2PG_FLAG_TIMING):
  * 0 seed (origination, in round 0 and later; the hop-limit passes of expiry rounds; the relay-policy
  * and downtime passes; the two anti-entropy passes of arrival rounds, k_pull_gather and

@@ -204,10 +204,15 @@ struct p2pg_engine {
   unsigned long long* d_tsent = nullptr;
   unsigned long long* d_trecv = nullptr;
   unsigned long long* d_tscratch = nullptr;
-  int32_t tally_pending = -1;   // the round whose sends the peer counters do not hold yet: they
+  // per-message cost (P2PG_FLAG_MSG_COST; k_msg_cost): sent / received [M] and its shard scratch
+  unsigned long long* d_csent = nullptr;
+  unsigned long long* d_crecv = nullptr;
+  unsigned long long* d_cscratch = nullptr;
+  int32_t tally_pending = -1;   // the round whose sends the peer / cost counters do not hold yet: they
                                 // are final (drops, removed connections) only at the next round's
                                 // start, in p2pg_update_edges or when the counters are read
-  int32_t tally_read_at = -1;   // e->round when p2pg_peer_counters took the pending round in
+  int32_t tally_read_at = -1;   // e->round when p2pg_peer_counters / p2pg_message_cost took the
+                                // pending round in
   // Start rounds (p2pg_set_sources_at / p2pg_originate): h_start[m] = the round message m
   // originates in at h_src[m] (0: round 0's seed; -1 with h_src[m] = -1: unscheduled).  The
   // messages that start after round 0 are kept on the device sorted by (round, peer, msg) and cut
@@ -321,6 +326,9 @@ void free_state(p2pg_engine* e) {
   dfree(e->d_tsent);
   dfree(e->d_trecv);
   dfree(e->d_tscratch);
+  dfree(e->d_csent);
+  dfree(e->d_crecv);
+  dfree(e->d_cscratch);
   DevState& s = e->st;
   dfree(s.seen);
   if (e->seen_spare) {
@@ -682,21 +690,33 @@ int ensure_pull(p2pg_engine* e) {
 // Run tallies (P2PG_FLAG_TALLY): every round keeps its whole frontier rows, which the column
 // count (at the round's end) and the peer pass (before the next round) read.
 bool tally_on(const p2pg_engine* e) { return (e->cfg.flags & P2PG_FLAG_TALLY) != 0; }
+// Per-message cost (P2PG_FLAG_MSG_COST): the pass over a round's final sends binned by message.
+bool cost_on(const p2pg_engine* e) { return (e->cfg.flags & P2PG_FLAG_MSG_COST) != 0; }
+// Is some pass deferred to the point where a round's sends are final (flush_peer_tally)?  Such an
+// engine keeps whole frontier rows and the pending-round bookkeeping.
+bool deferred_on(const p2pg_engine* e) { return tally_on(e) || cost_on(e); }
 // Does a round of this engine need its frontier rows whole (no skipped / partial rows, no
 // batched decay rounds)?
 // (a relay policy reads and rewrites the rows of every round: relay_policy.hip)
-bool frontier_needed(const p2pg_engine* e) { return count_lost_on(e) || tally_on(e) || e->pol_on; }
+bool frontier_needed(const p2pg_engine* e) { return count_lost_on(e) || deferred_on(e) || e->pol_on; }
 
-// Enqueue the peer counters of the pending round (its sends are final now): the sends leave on
+// Enqueue the peer counters and / or the per-message cost of the pending round (its sends are
+// final now): the sends leave on
 // gs (gone slots = connections removed while they were in flight), the round's own arrivals
 // travelled on graph_for_arrivals.  Stream order only, no host synchronisation.
 hipError_t flush_peer_tally(p2pg_engine* e, const DevGraph& gs) {
-  if (!tally_on(e) || e->tally_pending < 0) return hipSuccess;
+  if (!deferred_on(e) || e->tally_pending < 0) return hipSuccess;
   const int32_t r = e->tally_pending;
   e->tally_pending = -1;
   RoundParams p = params(e);
   p.round = r;
-  return launch_peer_tally(gs, graph_for_arrivals(e, r), e->st, p, down(e), pull_of(e, r), e->d_tsent, e->d_trecv, e->stream);
+  hipError_t x = hipSuccess;
+  if (tally_on(e))
+    x = launch_peer_tally(gs, graph_for_arrivals(e, r), e->st, p, down(e), pull_of(e, r), e->d_tsent, e->d_trecv, e->stream);
+  if (x == hipSuccess && cost_on(e))
+    x = launch_msg_cost(gs, graph_for_arrivals(e, r), e->st, p, down(e), pull_of(e, r), e->d_cscratch, e->d_csent,
+                        e->d_crecv, e->stream);
+  return x;
 }
 
 // Enqueue the count of round r's lost sends (k_sends, count mode) over gs (the graph the sends
@@ -807,6 +827,17 @@ int alloc_state(p2pg_engine* e) {
       return fail(e, P2PG_ERR_HIP, std::string("alloc_state (tallies): ") + hipGetErrorString(zr));
     }
   }
+  if (cost_on(e)) {  // M * 16 bytes and the cost pass's shards (p2pg_reset zeroes the counters)
+    const size_t sb = sizeof(unsigned long long) * (size_t)cost_scratch_words(e->W);
+    if ((rc = A((void**)&e->d_csent, sizeof(unsigned long long) * (size_t)e->M))) return rc;
+    if ((rc = A((void**)&e->d_crecv, sizeof(unsigned long long) * (size_t)e->M))) return rc;
+    if ((rc = A((void**)&e->d_cscratch, sb))) return rc;
+    const hipError_t zr = hipMemsetAsync(e->d_cscratch, 0, sb, e->stream);
+    if (zr != hipSuccess) {
+      free_state(e);
+      return fail(e, P2PG_ERR_HIP, std::string("alloc_state (message cost): ") + hipGetErrorString(zr));
+    }
+  }
 #ifdef P2PG_PROF
   if ((rc = A((void**)&s.prof, sizeof(unsigned long long) * 16))) return rc;
   HIPCHK(e, hipMemset(s.prof, 0, sizeof(unsigned long long) * 16));
@@ -830,6 +861,9 @@ int p2pg_create(const p2pg_config* cfg, p2pg_engine** out) {
     return fail(nullptr, P2PG_ERR_ARG, "create: gossip fanout must be in [1, 16]");
   if ((cfg->flags & P2PG_FLAG_TALLY) && (cfg->flags & P2PG_FLAG_LOCAL_GRAPH))
     return fail(nullptr, P2PG_ERR_ARG, "create: P2PG_FLAG_TALLY is not available on a vertex-partitioned rank "
+                                       "(P2PG_FLAG_LOCAL_GRAPH): ghost rows would be counted on two ranks");
+  if ((cfg->flags & P2PG_FLAG_MSG_COST) && (cfg->flags & P2PG_FLAG_LOCAL_GRAPH))
+    return fail(nullptr, P2PG_ERR_ARG, "create: P2PG_FLAG_MSG_COST is not available on a vertex-partitioned rank "
                                        "(P2PG_FLAG_LOCAL_GRAPH): ghost rows would be counted on two ranks");
   int ndev = 0;
   hipError_t r = hipGetDeviceCount(&ndev);
@@ -1679,6 +1713,10 @@ int p2pg_reset(p2pg_engine* e) {
     HIPCHK(e, hipMemsetAsync(e->d_tsent, 0, sizeof(unsigned long long) * (size_t)e->V, e->stream));
     HIPCHK(e, hipMemsetAsync(e->d_trecv, 0, sizeof(unsigned long long) * (size_t)e->V, e->stream));
   }
+  if (cost_on(e)) {
+    HIPCHK(e, hipMemsetAsync(e->d_csent, 0, sizeof(unsigned long long) * (size_t)e->M, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->d_crecv, 0, sizeof(unsigned long long) * (size_t)e->M, e->stream));
+  }
   e->tally_pending = -1;
   e->tally_read_at = -1;
   e->exp_pending = e->exp_final = -1;  // (the hop limits themselves stay and are replayed)
@@ -1809,7 +1847,7 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   HIPCHK(e, hipSetDevice(e->cfg.device));
   DevState& s = e->st;
   if (e->arr_round >= 0 && e->round > e->arr_round) {
-    if (tally_on(e)) HIPCHK(e, hipStreamSynchronize(e->stream));  // (the peer pass queued above reads it)
+    if (deferred_on(e)) HIPCHK(e, hipStreamSynchronize(e->stream));  // (the passes queued above read it)
     free_arr(e);
   }
   const DevGraph g = graph(e);
@@ -1968,8 +2006,8 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
                                              e->d_tscratch, nullptr, e->d_treach, e->d_thop, e->d_tlast,
                                              e->stream);
     if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("step (message tallies): ") + hipGetErrorString(x));
-    e->tally_pending = e->round;
   }
+  if (deferred_on(e)) e->tally_pending = e->round;
   if (xi >= 0) {
     // hop limits: the receive pass and k_originate counted every first receipt's relays; the
     // expired ones leave this round's total (round 0's are the host's: seed_stats).  Their frontier
@@ -2330,8 +2368,8 @@ int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32
     return fail(e, P2PG_ERR_STATE, "drop_relays: not available while anti-entropy is set (p2pg_set_anti_entropy)");
   int rc = sends_state(e, "drop_relays");
   if (rc) return rc;
-  if (tally_on(e) && e->tally_read_at == e->round)
-    return fail(e, P2PG_ERR_STATE, "drop_relays: p2pg_peer_counters has counted this round's sends already; "
+  if (deferred_on(e) && e->tally_read_at == e->round)
+    return fail(e, P2PG_ERR_STATE, "drop_relays: p2pg_peer_counters / p2pg_message_cost has counted this round's sends already; "
                                    "read the counters after the changes of a round boundary");
   if (n == 0) return P2PG_OK;
   if (e->d_gid || (e->cfg.flags & P2PG_FLAG_LOCAL_GRAPH))
@@ -2471,6 +2509,21 @@ static int tally_state(p2pg_engine* e, const char* what, bool need_flag) {
   return P2PG_OK;
 }
 
+// The pending round's sends count as they stand (p2pg_peer_counters, p2pg_message_cost): a later
+// drop or topology update at this boundary would change sends already counted, so those calls
+// refuse from here on.
+static int take_pending_round(p2pg_engine* e, const char* what) {
+  if (e->tally_pending < 0) return P2PG_OK;
+  {  // hop limits: the expired receipts' sends do not exist
+    const int xrc = finalize_expiry(e, true);
+    if (xrc) return xrc;
+  }
+  const hipError_t x = flush_peer_tally(e, graph(e));
+  if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string(what) + ": " + hipGetErrorString(x));
+  e->tally_read_at = e->round;
+  return P2PG_OK;
+}
+
 int p2pg_message_reach(p2pg_engine* e, uint64_t* reach) {
   int rc = tally_state(e, "message_reach", false);
   if (rc) return rc;
@@ -2514,17 +2567,7 @@ int p2pg_peer_counters(p2pg_engine* e, uint64_t* sent, uint64_t* received) {
   int rc = tally_state(e, "peer_counters", true);
   if (rc) return rc;
   HIPCHK(e, hipSetDevice(e->cfg.device));
-  if (e->tally_pending >= 0) {
-    {  // hop limits: the expired receipts' sends do not exist
-      const int xrc = finalize_expiry(e, true);
-      if (xrc) return xrc;
-    }
-    // the last round's sends count as they stand: a later drop or topology update at this
-    // boundary would change sends already counted, so those calls refuse from here on
-    const hipError_t x = flush_peer_tally(e, graph(e));
-    if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("peer_counters: ") + hipGetErrorString(x));
-    e->tally_read_at = e->round;
-  }
+  if ((rc = take_pending_round(e, "peer_counters"))) return rc;
   HIPCHK(e, hipStreamSynchronize(e->stream));
   const size_t n = (size_t)e->V;
   if (sent) HIPCHK(e, hipMemcpy(sent, e->d_tsent, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
@@ -2532,10 +2575,28 @@ int p2pg_peer_counters(p2pg_engine* e, uint64_t* sent, uint64_t* received) {
   return P2PG_OK;
 }
 
+int p2pg_message_cost(p2pg_engine* e, uint64_t* sent, uint64_t* received) {
+  int rc = tally_state(e, "message_cost", false);
+  if (rc) return rc;
+  if (!cost_on(e)) return fail(e, P2PG_ERR_STATE, "message_cost: needs P2PG_FLAG_MSG_COST");
+  if (e->d_gid || (e->cfg.flags & P2PG_FLAG_LOCAL_GRAPH))
+    return fail(e, P2PG_ERR_STATE, "message_cost: not on a vertex-partitioned rank");
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  if ((rc = take_pending_round(e, "message_cost"))) return rc;
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  const size_t n = (size_t)e->M;
+  if (sent) HIPCHK(e, hipMemcpy(sent, e->d_csent, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+  if (received) HIPCHK(e, hipMemcpy(received, e->d_crecv, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+  return P2PG_OK;
+}
+
 int p2pg_set_global_ids(p2pg_engine* e, const int32_t* gid) {
   if (!e || !e->d_rowptr) return fail(e, P2PG_ERR_STATE, "set_global_ids: load a graph first");
   if (tally_on(e))
     return fail(e, P2PG_ERR_STATE, "set_global_ids: a P2PG_FLAG_TALLY engine cannot be a vertex-partitioned "
+                                   "rank (ghost rows would be counted on two ranks)");
+  if (cost_on(e))
+    return fail(e, P2PG_ERR_STATE, "set_global_ids: a P2PG_FLAG_MSG_COST engine cannot be a vertex-partitioned "
                                    "rank (ghost rows would be counted on two ranks)");
   if (gid && e->have_state && e->late)
     return fail(e, P2PG_ERR_STATE, "set_global_ids: start rounds other than 0 are not available on a "
@@ -2766,8 +2827,8 @@ int p2pg_update_edges(p2pg_engine* e, int64_t n_add, const int32_t* add, int64_t
   if (e->arr_round >= 0 && e->arr_round == e->round)
     return fail(e, P2PG_ERR_STATE, "update_edges: one update per round boundary");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "update_edges: a round has begun (step_begin)");
-  if (tally_on(e) && e->have_state && e->tally_read_at == e->round)
-    return fail(e, P2PG_ERR_STATE, "update_edges: p2pg_peer_counters has counted this round's sends already; "
+  if (deferred_on(e) && e->have_state && e->tally_read_at == e->round)
+    return fail(e, P2PG_ERR_STATE, "update_edges: p2pg_peer_counters / p2pg_message_cost has counted this round's sends already; "
                                    "read the counters after the changes of a round boundary");
   const int64_t V = e->V;
   const std::vector<int64_t>& rp = e->h_rowptr;
@@ -2852,7 +2913,7 @@ int p2pg_update_edges(p2pg_engine* e, int64_t n_add, const int32_t* add, int64_t
       gs.gone = d_gone;
       gr = flush_peer_tally(e, gs);
       // (it reads the arrival graph freed below)
-      if (gr == hipSuccess && tally_on(e)) gr = hipStreamSynchronize(e->stream);
+      if (gr == hipSuccess && deferred_on(e)) gr = hipStreamSynchronize(e->stream);
     }
     if (gr != hipSuccess) {
       (void)hipFree(d_gone);
@@ -2916,7 +2977,7 @@ int p2pg_update_edges(p2pg_engine* e, int64_t n_add, const int32_t* add, int64_t
     e->d_rowptr = nullptr;
     e->d_colidx = nullptr;
     e->arr_round = e->round;
-  } else if (tally_on(e) && e->tally_pending >= 0) {
+  } else if (deferred_on(e) && e->tally_pending >= 0) {
     // a finished run: its last round's sends (none pass a quiet round) over the graph they left on
     hipError_t x = flush_peer_tally(e, graph(e));
     if (x == hipSuccess) x = hipStreamSynchronize(e->stream);
@@ -3013,6 +3074,8 @@ int p2pg_snapshot(p2pg_engine* e, void* buf, int64_t cap) {
   if (!e->have_state) return fail(e, P2PG_ERR_STATE, "snapshot: no sources set");
   if (tally_on(e))
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold run tallies (P2PG_FLAG_TALLY)");
+  if (cost_on(e))
+    return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold the per-message cost (P2PG_FLAG_MSG_COST)");
   if (e->late)
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold start rounds other than 0 "
                                    "(p2pg_set_sources_at / p2pg_originate)");
@@ -3087,6 +3150,8 @@ int p2pg_restore(p2pg_engine* e, const void* buf, int64_t size) {
   if (!e->have_state) return fail(e, P2PG_ERR_STATE, "restore: set the same sources first");
   if (tally_on(e))
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold run tallies (P2PG_FLAG_TALLY)");
+  if (cost_on(e))
+    return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold the per-message cost (P2PG_FLAG_MSG_COST)");
   if (e->late)
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold start rounds other than 0 "
                                    "(p2pg_set_sources_at / p2pg_originate)");

@@ -5,7 +5,10 @@
 //     frontier: its first receipts, from which reach / hop_sum / last_hop accumulate);
 //   * k_peer_tally: Node.message_count_send (node.py:65, :116) and message_count_recv
 //     (nodeconnection.py:215) per peer, from the same send set relay_sends.hip's k_sends
-//     enumerates, accumulated instead of emitted.
+//     enumerates, accumulated instead of emitted;
+//   * k_msg_cost (p2pg_message_cost): the same send set accumulated per message -- the
+//     send_to_node calls that carried payload id m (node.py:116) and those of them that arrived
+//     (nodeconnection.py:215).
 // Opt-in passes outside the rounds' own kernels.  Internal; not part of the C-ABI.
 #include "device_util.h"
 
@@ -344,7 +347,351 @@ __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, De
   }
 }
 
+// ---- per-message cost ----------------------------------------------------------------------
+
+// Vertical counters that take a multi-bit addend: COST_PLANES planes hold up to COST_CAP per bit
+// of the lane's word.  The addend is wave-uniform (a peer's degree, its connections that are not
+// lost, the fanout), so each plane's operand is the mask or nothing: one full-adder step per plane,
+// whatever the number of set bits.  A flood receipt's sender takes 1 back off (a ripple borrow).
+constexpr int COST_PLANES = 8;
+constexpr uint32_t COST_CAP = (1u << COST_PLANES) - 1u;
+constexpr int COST_LIST = 2048;            // receipts listed per pass of the pick redraw
+// A wave takes the block's LDS counts (32 bits) out to the shards before the weight it has added
+// since it last did so passes this: 4 waves x 2^29 stay below 2^32 per count.
+constexpr uint32_t COST_DRAIN = 1u << 29;
+constexpr int COST_LDS_SHIFT = 5;           // one addend above COST_DRAIN >> 5 goes to the shards directly
+
+struct WCount {
+  uint64_t c[COST_PLANES];
+};
+
+__device__ __forceinline__ void wc_add(WCount& k, uint32_t wgt, uint64_t m) {
+  uint64_t carry = 0ull;
+#pragma unroll
+  for (int i = 0; i < COST_PLANES; ++i) {
+    const uint64_t a = k.c[i];
+    const uint64_t b = ((wgt >> i) & 1u) ? m : 0ull;
+    const uint64_t x = a ^ b;
+    k.c[i] = x ^ carry;
+    carry = (a & b) | (carry & x);
+  }
+}
+
+__device__ __forceinline__ void wc_sub1(WCount& k, uint64_t m) {
+  uint64_t borrow = m;
+#pragma unroll
+  for (int i = 0; i < COST_PLANES; ++i) {
+    const uint64_t a = k.c[i];
+    k.c[i] = a ^ borrow;
+    borrow &= ~a;
+  }
+}
+
+// LDS count of bit b of word `word` of the block's slice (k_colcount's rotation: the 64 lanes of
+// one instruction spread over the banks).
+__device__ __forceinline__ int cost_idx(int word, int b) { return word * 64 + ((b + word) & 63); }
+
+// The lane's nonzero counts to its row of lds[64][64]; only the bits that hold something are
+// visited (a tail round has one or two per word).
+__device__ __forceinline__ void wc_flush(WCount& k, uint32_t* lds, int lane) {
+  uint64_t any = 0ull;
+#pragma unroll
+  for (int i = 0; i < COST_PLANES; ++i) any |= k.c[i];
+  while (any) {
+    const int b = __builtin_ctzll(any);
+    any &= any - 1ull;
+    uint32_t v = 0u;
+#pragma unroll
+    for (int i = 0; i < COST_PLANES; ++i) v |= ((uint32_t)(k.c[i] >> b) & 1u) << i;
+    atomicAdd(&lds[cost_idx(lane, b)], v);
+  }
+#pragma unroll
+  for (int i = 0; i < COST_PLANES; ++i) k.c[i] = 0ull;
+}
+
+// sent[m] / received[m] of round r = p.round, per message instead of per peer: k_peer_tally's send
+// set (same send_lost, gone slots, find_slot when gs != gp, anti-entropy partner), summed over the
+// bit columns of the frontier rows.  Block items are slice-major as in k_colcount (one 64-word
+// slice at a time, the block's LDS counts leave when its slice changes); a wave's task is the
+// active peers of one 32-peer word of A, lane = word of the slice.  Per peer v and word f:
+// Flood, and gossip with deg <= k: every bit adds deg to sent and nl(v) -- v's connections whose
+//   send is not lost, counted once per peer -- to received; in flood rounds r > 0 a bit whose sender
+//   (k_peer_tally's walk) is still a connection takes 1 back off sent, and off received if the send
+//   towards that sender would not have been lost.
+// Gossip, deg > k: every bit adds k to sent.  If none of v's connections loses its send (always so
+//   without churn, removed slots and downtime) it adds k to received as well and no pick is drawn;
+//   else the picks are re-drawn over a lane-balanced list of the slice's receipts and each receipt
+//   adds its picks that are not lost (looked up in the peer's bitmap of lost connections; rows
+//   above HUB_T connections test per pick), one LDS atomic per receipt.
+// Addends above COST_CAP (hubs) skip the vertical counters: one LDS atomic per set bit and counter,
+// or, above drain_at >> COST_LDS_SHIFT (2^24 connections), one 64-bit atomic into the shard.
+// drain_at: COST_DRAIN (a launch argument so that a test can reach the drain and that last path).
+__global__ __launch_bounds__(256) void k_msg_cost(DevGraph gs, DevGraph gp, DevState st, RoundParams p,
+                                                  Downtime d, Pull pl, unsigned long long* __restrict__ scratch,
+                                                  int shards, uint32_t drain_at) {
+  __shared__ uint32_t lds_s[64 * 64];
+  __shared__ uint32_t lds_r[64 * 64];
+  __shared__ uint16_t lst_all[WPB][COST_LIST];
+  __shared__ uint32_t lostmap_all[WPB][HUB_T / 32];
+  const int lane = threadIdx.x & 63;
+  const int wib = wave_in_block();
+  uint16_t* lst = lst_all[wib];
+  uint32_t* lostmap = lostmap_all[wib];
+  const int cur = p.round & 1;
+  const int W = st.W;
+  const int nsl = (W + 63) >> 6;
+  const size_t nmsg = (size_t)nsl * 4096;
+  const int64_t ntasks = (gs.V + 31) >> 5;
+  const int64_t nbt = (ntasks + WPB - 1) / WPB;
+  const int64_t nitems = nbt * nsl;
+  const bool same = gs.rowptr == gp.rowptr && gs.colidx == gp.colidx;
+  const bool lossless = !gs.gone && !p.churn_thr && !d.from;
+  const uint32_t lds_max = drain_at >> COST_LDS_SHIFT;
+  unsigned long long* out_s = scratch + (size_t)(blockIdx.x & (shards - 1)) * (2 * nmsg);
+  unsigned long long* out_r = out_s + nmsg;
+  WCount ks, kr;
+#pragma unroll
+  for (int i = 0; i < COST_PLANES; ++i) ks.c[i] = kr.c[i] = 0ull;
+  uint32_t held = 0u;   // upper bound of any count in ks / kr (wave-uniform)
+  uint32_t added = 0u;  // upper bound of what this wave added to any LDS count since its last drain
+  for (int i = threadIdx.x; i < 64 * 64; i += 256) lds_s[i] = lds_r[i] = 0u;
+  __syncthreads();
+  // LDS index i of slice sl -> entry of a shard (word-major, unrotated)
+  auto shard_at = [&](int sl, int i) -> int64_t {
+    const int word = i >> 6;
+    const int gw = sl * 64 + word;
+    return gw < W ? (int64_t)gw * 64 + (((i & 63) - word) & 63) : -1;
+  };
+  // Takes whatever the LDS counts hold out to the shards.  Exchanges, so any wave may do it while
+  // the others keep adding: an add lands before the exchange or after it.
+  auto drain = [&](int sl, int first, int step) {
+    for (int i = first; i < 64 * 64; i += step) {
+      const int64_t at = shard_at(sl, i);
+      const uint32_t vs = lds_s[i] ? atomicExch(&lds_s[i], 0u) : 0u;
+      const uint32_t vr = lds_r[i] ? atomicExch(&lds_r[i], 0u) : 0u;
+      if (vs && at >= 0) atomicAdd(out_s + at, (unsigned long long)vs);
+      if (vr && at >= 0) atomicAdd(out_r + at, (unsigned long long)vr);
+    }
+  };
+  auto block_flush = [&](int sl) {  // block-uniform calls only; leaves the LDS counts zero
+    wc_flush(ks, lds_s, lane);
+    wc_flush(kr, lds_r, lane);
+    held = 0u;
+    __syncthreads();
+    drain(sl, threadIdx.x, 256);
+    added = 0u;
+    __syncthreads();
+  };
+  // before an addend of wgt per bit: room in the vertical counters and in the LDS counts
+  auto make_room = [&](int sl, uint32_t wgt) {
+    if (wgt > lds_max) return;  // (add_wide: straight to the shards)
+    if (wgt <= COST_CAP && held + wgt > COST_CAP) {
+      wc_flush(ks, lds_s, lane);
+      wc_flush(kr, lds_r, lane);
+      held = 0u;
+    }
+    if (added + wgt > drain_at) {
+      wc_flush(ks, lds_s, lane);
+      wc_flush(kr, lds_r, lane);
+      held = 0u;
+      wave_lds_sync();
+      drain(sl, lane, 64);
+      added = 0u;
+    }
+    added += wgt;
+    if (wgt <= COST_CAP) held += wgt;
+  };
+  // a peer whose degree is above COST_CAP: wgt, or wgt - 1 under less1, per set bit of f
+  auto add_wide = [&](int sl, uint32_t* lds, unsigned long long* out, uint64_t f, uint32_t wgt, uint64_t less1,
+                      bool to_lds) {
+    while (f) {
+      const int b = __builtin_ctzll(f);
+      f &= f - 1ull;
+      const uint32_t v = wgt - (uint32_t)((less1 >> b) & 1ull);
+      if (!v) continue;
+      if (to_lds) {
+        atomicAdd(&lds[cost_idx(lane, b)], v);
+      } else {
+        const int gw = sl * 64 + lane;
+        atomicAdd(out + (int64_t)gw * 64 + b, (unsigned long long)v);  // (f != 0: gw < W)
+      }
+    }
+  };
+  int cur_sl = -1;
+  for (int64_t bi = blockIdx.x; bi < nitems; bi += gridDim.x) {
+    const int sl = (int)(bi / nbt);
+    if (sl != cur_sl) {
+      if (cur_sl >= 0) block_flush(cur_sl);
+      cur_sl = sl;
+    }
+    const int64_t task = (bi - (int64_t)sl * nbt) * WPB + wib;
+    if (task >= ntasks) continue;
+    const int w = sl * 64 + lane;
+    uint32_t aw = st.A[cur][task];
+    while (aw) {
+      const int b = __builtin_ctz(aw);
+      aw &= aw - 1u;
+      const int64_t v = (task << 5) + b;
+      const int64_t beg = gs.rowptr[v], end = gs.rowptr[v + 1];
+      if (beg == end) continue;
+      const uint64_t f = w < W ? st.F[cur][v * W + w] : 0ull;
+      if (!__ballot(f != 0ull)) continue;
+      const uint32_t deg = (uint32_t)(end - beg);
+      const bool picks = p.mode != 0 && (int)deg > p.fanout;
+      // v's connections whose send is lost, tested once per connection: their number, and for a
+      // peer that draws picks (rows of at most HUB_T connections) their bitmap in LDS
+      const bool use_map = picks && deg <= (uint32_t)HUB_T;
+      uint32_t nlost = 0u;
+      if (!lossless) {
+        for (int64_t j0 = beg; j0 < end; j0 += 64) {
+          const int64_t j = j0 + lane;
+          const uint64_t bal = __ballot(j < end && send_lost(gs, p, d, v, gs.colidx[j], j));
+          nlost += (uint32_t)__popcll(bal);
+          if (use_map && lane < 2) lostmap[((j0 - beg) >> 5) + lane] = (uint32_t)(bal >> (32 * lane));
+        }
+        if (use_map) wave_lds_sync();
+      }
+      if (!picks) {
+        const uint32_t nl = deg - nlost;  // connections whose send is not lost
+        uint64_t ex_s = 0ull, ex_r = 0ull;  // bits whose sender gets no copy / would have got one
+        if (p.mode == 0 && p.round > 0) {
+          const int32_t partner = pl.R && bit_test(pl.PB, v) ? pull_partner(gp, pl, p.round - 2, v) : -1;
+          uint64_t rem = f;
+          const uint64_t pw = partner >= 0 ? pull_word(st, pl, v, w) : 0ull;
+          const int64_t ep = gp.rowptr[v + 1];
+          for (int64_t jp = gp.rowptr[v]; jp < ep && __ballot(rem != 0ull); ++jp) {
+            const int32_t y = gp.colidx[jp];
+            const uint64_t sy = prev_sends(gp, st, p, v, y, jp, w) | (y == partner ? pw : 0ull);
+            const uint64_t pu = rem & sy;
+            rem &= ~sy;
+            if (!__ballot(pu != 0ull)) continue;
+            const int64_t j = same ? jp : find_slot(gs, beg, end, y);
+            if (j < 0) continue;  // no longer a connection: nothing was sent to it
+            ex_s |= pu;
+            if (!send_lost(gs, p, d, v, y, j)) ex_r |= pu;
+          }
+        }
+        make_room(sl, deg);
+        if (deg <= COST_CAP && deg <= lds_max) {
+          wc_add(ks, deg, f);
+          wc_sub1(ks, ex_s);
+          wc_add(kr, nl, f);
+          wc_sub1(kr, ex_r);  // (a sender whose copy is not lost is one of the nl)
+        } else {
+          add_wide(sl, lds_s, out_s, f, deg, ex_s, deg <= lds_max);
+          add_wide(sl, lds_r, out_r, f, nl, ex_r, deg <= lds_max);
+        }
+      } else {
+        const uint32_t k = (uint32_t)p.fanout;  // <= 16
+        make_room(sl, k);
+        wc_add(ks, k, f);
+        if (!nlost) {  // every pick arrives, whichever it is
+          wc_add(kr, k, f);
+          continue;
+        }
+        // the slice's receipts as a list of message indices in LDS (k_peer_tally), COST_LIST per pass
+        const uint32_t pc = (uint32_t)__popcll(f);
+        const uint32_t pos0 = wave_scan_u32(pc) - pc;
+        const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)(pos0 + pc), 63);
+        auto count = [&](uint32_t m, const uint32_t* pk, int K) {
+          uint32_t c = 0u;
+          for (int q = 0; q < K; ++q) {
+            if (use_map) {
+              c += 1u - ((lostmap[pk[q] >> 5] >> (pk[q] & 31u)) & 1u);
+            } else {
+              const int64_t j = beg + (int64_t)pk[q];
+              if (!send_lost(gs, p, d, v, gs.colidx[j], j)) ++c;
+            }
+          }
+          if (c) atomicAdd(&lds_r[cost_idx((int)(m >> 6), (int)(m & 63u))], c);
+        };
+        for (uint32_t base = 0; base < n; base += COST_LIST) {
+          uint32_t pos = pos0 - base;  // (wraps below the window: never < COST_LIST then)
+          uint64_t o = f;
+          while (o) {
+            if (pos < (uint32_t)COST_LIST) lst[pos] = (uint16_t)(lane * 64 + __builtin_ctzll(o));
+            ++pos;
+            o &= o - 1ull;
+          }
+          wave_lds_sync();
+          const uint32_t cnt = n - base < (uint32_t)COST_LIST ? n - base : (uint32_t)COST_LIST;
+          auto draw = [&](auto kc) {  // fanout <= 4: one Philox block per receipt
+            constexpr int K = decltype(kc)::value;
+            const PickKey key = pick_key((uint32_t)p.round, gidx(gs, v), p.gseed_lo, p.gseed_hi);
+            for (uint32_t i = lane; i < cnt; i += 64) {
+              uint32_t pk[K];
+              const uint32_t m = lst[i];
+              gossip_picks_k<K>(key, p.msg_base + (uint32_t)(sl * 4096) + m, deg, pk);
+              count(m, pk, K);
+            }
+          };
+          switch (p.fanout) {
+            case 1: draw(std::integral_constant<int, 1>{}); break;
+            case 2: draw(std::integral_constant<int, 2>{}); break;
+            case 3: draw(std::integral_constant<int, 3>{}); break;
+            case 4: draw(std::integral_constant<int, 4>{}); break;
+            default:
+              for (uint32_t i = lane; i < cnt; i += 64) {
+                uint32_t pk[16];
+                const uint32_t m = lst[i];
+                gossip_picks((uint32_t)p.round, gidx(gs, v), p.msg_base + (uint32_t)(sl * 4096) + m, deg, p.fanout,
+                             p.gseed_lo, p.gseed_hi, pk);
+                count(m, pk, p.fanout);
+              }
+          }
+          wave_lds_sync();  // (the next pass rewrites the list)
+        }
+      }
+    }
+  }
+  if (cur_sl >= 0) block_flush(cur_sl);
+}
+
+// sent[m] += / received[m] += the shards' sums (n entries per counter and shard; entry m = message
+// m), which are left zero for the next round.  Entries at or above M hold nothing.
+__global__ __launch_bounds__(256) void k_cost_fold(unsigned long long* __restrict__ scratch, int shards, int64_t n,
+                                                   int32_t M, unsigned long long* __restrict__ sent,
+                                                   unsigned long long* __restrict__ received) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  unsigned long long cs = 0, cr = 0;
+  for (int s = 0; s < shards; ++s) {
+    unsigned long long* sh = scratch + (size_t)s * (2 * (size_t)n);
+    cs += sh[i];
+    cr += sh[n + i];
+    sh[i] = 0ull;
+    sh[n + i] = 0ull;
+  }
+  if (i >= M) return;
+  if (cs) sent[i] += cs;
+  if (cr) received[i] += cr;
+}
+
 }  // namespace
+
+int64_t cost_scratch_words(int32_t W) { return (int64_t)TALLY_SHARDS * 2 * ((W + 63) / 64) * 4096; }
+
+hipError_t launch_msg_cost(const DevGraph& gs, const DevGraph& gp, const DevState& st, const RoundParams& p,
+                           const Downtime& d, const Pull& pl, unsigned long long* scratch,
+                           unsigned long long* sent, unsigned long long* received, hipStream_t s) {
+  if (gs.V <= 0 || st.W <= 0) return hipSuccess;
+  static const uint32_t drain_at = [] {  // P2PG_COST_DRAIN: the tests' way to the LDS drain
+    const char* e = std::getenv("P2PG_COST_DRAIN");
+    const long v = e ? std::atol(e) : 0;
+    // (at least 16 << COST_LDS_SHIFT: the fanout always goes through the vertical counters)
+    return v >= (16l << COST_LDS_SHIFT) && v < (long)COST_DRAIN ? (uint32_t)v : COST_DRAIN;
+  }();
+  const int nsl = (st.W + 63) / 64;
+  const int64_t n = (int64_t)nsl * 4096;
+  const int64_t nbt = (((gs.V + 31) >> 5) + WPB - 1) / WPB;
+  hipLaunchKernelGGL(k_msg_cost, dim3(grid_tasks(nbt * nsl * WPB)), dim3(256), 0, s, gs, gp, st, p, d, pl, scratch,
+                     TALLY_SHARDS, drain_at);
+  hipError_t r = hipGetLastError();
+  if (r != hipSuccess) return r;
+  hipLaunchKernelGGL(k_cost_fold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scratch, TALLY_SHARDS, n,
+                     st.M, sent, received);
+  return hipGetLastError();
+}
 
 int64_t tally_scratch_words(int32_t W) { return (int64_t)TALLY_SHARDS * ((W + 63) / 64) * 4096; }
 

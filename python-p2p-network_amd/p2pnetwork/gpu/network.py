@@ -103,6 +103,10 @@ MessageTally = namedtuple("MessageTally", "reach hop_sum last_hop")
 # ... and per peer, uint64 [V]: Node.message_count_send (node.py:65, :116) and
 # message_count_recv (nodeconnection.py:215) -- p2pg_peer_counters
 PeerCounters = namedtuple("PeerCounters", "sent received")
+# Per-broadcast cost (GraphNetwork(cost=True)), uint64 [M]: the send_to_node calls that carried
+# each broadcast (node.py:116) and those of them that arrived (nodeconnection.py:215) --
+# p2pg_message_cost
+MessageCost = namedtuple("MessageCost", "sent received")
 
 # index of SnapHeader.total_relays in the snapshot header viewed as uint64 words (engine.cpp:
 # magic 0, version/mode 1, V 2, nnz 3, M/W 4, fanout/round 5, flags/thr 6, base/done 7,
@@ -137,7 +141,7 @@ class GraphNetwork:
     def __init__(self, graph, mode="flood", fanout=3, gossip_seed=0x5EED, churn=0.0,
                  churn_threshold_value=None, churn_seed=0xC0FFEE, record=False, timing=False,
                  device=0, msg_id_base=0, callback=None, autostop=True, local_graph=False,
-                 count_received=False, tally=False):
+                 count_received=False, tally=False, cost=False):
         if not isinstance(graph, PeerGraph):
             raise TypeError("graph must be a PeerGraph")
         if mode not in ("flood", "gossip"):
@@ -159,7 +163,8 @@ class GraphNetwork:
                      | (0 if autostop else _lib.FLAG_NO_AUTOSTOP)
                      | (_lib.FLAG_LOCAL_GRAPH if local_graph else 0)
                      | (_lib.FLAG_RECEIVED if count_received else 0)
-                     | (_lib.FLAG_TALLY if tally else 0))
+                     | (_lib.FLAG_TALLY if tally else 0)
+                     | (_lib.FLAG_MSG_COST if cost else 0))
         cfg.device = int(device)
         self.config = cfg
         L = _lib.lib()
@@ -643,6 +648,28 @@ class GraphNetwork:
         received = np.zeros(self.graph.V, dtype=np.uint64)
         self._check(_lib.lib().p2pg_peer_counters(self._h, _lib.ptr(sent), _lib.ptr(received)))
         return PeerCounters(sent, received)
+
+    def message_cost(self):
+        """MessageCost(sent, received) per broadcast: the send_to_node calls that carried it in
+        the rounds run so far (lost ones included, withdrawn relays not) and those of them that
+        arrived; needs cost=True.  The records of ``sends()`` binned by message.  Read it after a
+        round boundary's drop_relays / update_edges, as ``peer_counters()`` (p2pg_message_cost)."""
+        sent = np.zeros(self.M, dtype=np.uint64)
+        received = np.zeros(self.M, dtype=np.uint64)
+        self._check(_lib.lib().p2pg_message_cost(self._h, _lib.ptr(sent), _lib.ptr(received)))
+        return MessageCost(sent, received)
+
+    def message_redundancy(self):
+        """float64 [M]: the relative message redundancy of each broadcast, sent / (reach - 1) - 1
+        (0 = every peer reached got exactly one copy, as over a spanning tree); NaN where the
+        broadcast reached nobody but its origin.  Host arithmetic on ``message_cost()`` and
+        ``message_reach()``; needs cost=True."""
+        sent = self.message_cost().sent.astype(np.float64)
+        reach = self.message_reach().astype(np.float64)
+        out = np.full(self.M, np.nan)
+        ok = reach > 1
+        out[ok] = sent[ok] / (reach[ok] - 1.0) - 1.0
+        return out
 
     def hop_parent(self, relative=False):
         """(hop, parent) int32 [V, M]; needs record=True.  -1 = not delivered / origin.  Hops are

@@ -235,9 +235,12 @@ class PartitionedNetwork:
 
     def __init__(self, graph, world, rank, transport, mode="flood", fanout=3, gossip_seed=0x5EED,
                  churn_threshold_value=0, churn_seed=0xC0FFEE, record=False, timing=False,
-                 device=0, engine_factory=None, overlap=True, deliveries=False, msg_id_base=0, tally=False):
+                 device=0, engine_factory=None, overlap=True, deliveries=False, msg_id_base=0, tally=False,
+                 cost=False):
         if tally:  # (ghost rows would be counted on two ranks; include/p2pgpu.h P2PG_FLAG_TALLY)
             raise ValueError("run tallies are not available on a vertex-partitioned network")
+        if cost:  # (likewise: P2PG_FLAG_MSG_COST)
+            raise ValueError("the per-message cost is not available on a vertex-partitioned network")
         if not 1 <= world <= MAX_RANKS:
             raise ValueError(f"vertex partition over {world} ranks: the exchange supports 1..{MAX_RANKS}")
         self.world, self.rank, self.transport = world, rank, transport
