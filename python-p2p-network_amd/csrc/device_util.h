@@ -61,6 +61,18 @@ __device__ __forceinline__ uint32_t wave_scan_u32(uint32_t x) {
   return x;
 }
 
+// wave_scan_u32 for the entry scans of the gossip pushes (scatter_row, scatter_wide), whose
+// callers also use the exclusive prefix incl - x.  There the compiler rewrites that difference as
+// the sum of the six shifted terms, which keeps every v_mov_b32_dpp result alive for a second use,
+// so none of them folds into its add: a zeroing move, the DPP move and the add per step (18 VALU).
+// The opaque result makes incl - x one subtract, and the steps are six v_add_u32_dpp.
+__device__ __forceinline__ uint32_t wave_scan_excl_u32(uint32_t x, uint32_t& incl) {
+  uint32_t s = wave_scan_u32(x);
+  asm("" : "+v"(s));
+  incl = s;
+  return s - x;
+}
+
 __device__ __forceinline__ void flush_stats(unsigned long long* stats, const uint64_t* c,
                                             int lane) {
   unsigned long long* shard = stats + (blockIdx.x & (STAT_SHARDS - 1)) * STAT_N;

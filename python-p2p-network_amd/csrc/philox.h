@@ -204,6 +204,39 @@ P2PG_HD void gossip_picks_k(const PickKey& key, uint32_t msg, uint32_t n, uint32
   }
 }
 
+#if defined(__HIPCC__)
+// gossip_picks_k inside a loop over one source's messages (the pick batches of a push).  There the
+// compiler widens Floyd's duplicate tests to 64 bits (the multiply-high results zero-extended: a
+// zero moved into a high half per compare) and copies the wave-uniform bounds n - K + i from
+// scalar into vector registers once per message for the selects.  pick_bounds() puts the bounds
+// into vector registers once per source; gossip_picks_kb() takes them and keeps each draw an
+// opaque 32-bit value, so the compares stay 32-bit.  Same draws, same order, same results.
+template <int K>
+__device__ __forceinline__ void pick_bounds(uint32_t n, uint32_t (&jm)[K]) {
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    jm[i] = n - (uint32_t)K + (uint32_t)i;
+    if (i > 0) asm("" : "+v"(jm[i]));  // (draw 0 has no earlier pick to collide with)
+  }
+}
+
+template <int K>
+__device__ __forceinline__ void gossip_picks_kb(const PickKey& key, uint32_t msg, uint32_t n,
+                                                const uint32_t (&jm)[K], uint32_t (&out)[K]) {
+  static_assert(K >= 1 && K <= 4, "one Philox block");
+  const u32x4 r = philox_pick(key, msg);
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    uint32_t t = lemire32(word_of(r, i), n - (uint32_t)K + (uint32_t)i + 1u);
+    if (K > 1) asm("" : "+v"(t));
+    bool dup = false;
+#pragma unroll
+    for (int q = 0; q < i; ++q) dup |= (out[q] == t);
+    out[i] = dup ? jm[i] : t;
+  }
+}
+#endif
+
 // Churn: a send over undirected edge {a,b} made in round r is lost iff the
 // first Philox word is below the threshold floor(p_drop * 2^32).
 P2PG_HD bool churn_dropped(uint32_t round, uint32_t a, uint32_t b, uint32_t threshold,

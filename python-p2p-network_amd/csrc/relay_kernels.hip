@@ -1111,34 +1111,64 @@ __global__ __launch_bounds__(256) void k_materialize(DevGraph g, DevState st, Ro
 #define P2PG_PICK_DUP 1
 #endif
 
+// A/B switches of the narrow sender's push (profiles/narrow_push; 0 = the form before):
+// P2PG_NP_SCAN: the entry scan's six DPP steps fold into their adds (wave_scan_excl_u32);
+// P2PG_NP_CELL64: the mask table's two halves of a word are adjacent (a 64-bit cell);
+// P2PG_NP_CMP32: Floyd's duplicate tests stay 32-bit and select from bounds kept in registers.
+#ifndef P2PG_NP_SCAN
+#define P2PG_NP_SCAN 1
+#endif
+#ifndef P2PG_NP_CELL64
+#define P2PG_NP_CELL64 1
+#endif
+#ifndef P2PG_NP_CMP32
+#define P2PG_NP_CMP32 1
+#endif
+
 // LDS of one scatter wave: a GCHUNK x 64-word mask table (two 32-bit halves per word, so
 // 32-bit LDS atomics) and the compacted list of active (word, bit) entries.
-// Half-major rows: connection j's row is [half][word], so the
-// 64 lanes of a pick batch -- entries of ~64 different words -- OR into 64 different banks;
-// with the halves adjacent ([word][half], a 64-bit LDS access per mask) words w and w+32 share
-// a bank (2-way conflicts: 40-49 % of the fused kernel's LDS cycles, profiles/r01/pmc_sq_v11).
+// Compile-time fanouts (P2PG_NP_CELL64): connection j's row is [word][half], a mask is one 64-bit
+// cell, so a list entry e = word << 6 | bit names its half as e >> 5, the flush reads a mask with
+// one 64-bit LDS access and the clear is one write.  Words w and w + 32 then share a bank; by the
+// counters the conflict share of the LDS cycles goes from 40.6 to 42.3 % over a c4 broadcast (peak
+// rounds 46.8 -> 49.0 %, the lightest 58.8 -> 56.8 %), for 1.2 % fewer VALU (profiles/narrow_push).
+// Generic fanout: half-major rows, connection j's row is [half][word], so the 64 lanes of a pick
+// batch -- entries of ~64 different words -- OR into 64 different banks.  (The cells cost the
+// generic-fanout W <= 32 instance of the fused kernel its fourth wave per SIMD, 128 -> 130 VGPRs.)
 struct ScatterLds {
   alignas(8) uint32_t tbl[GCHUNK * 128];
   uint16_t lst[GLIST];
 };
 
-// u32 index of half h of (connection j, word w)
+// u32 index of half h of (connection j, word w); CELL: the 64-bit cells
+template <bool CELL>
 __device__ __forceinline__ uint32_t tbl_ix(uint32_t j, uint32_t w, uint32_t h) {
-  return j * 128u + h * 64u + w;
+  return CELL ? j * 128u + w * 2u + h : j * 128u + h * 64u + w;
 }
 
 // u32 index of list entry e = word << 6 | bit in connection 0's row
+template <bool CELL>
 __device__ __forceinline__ uint32_t tbl_entry_ix(uint32_t e) {
-  return tbl_ix(0u, e >> 6, (e >> 5) & 1u);
+  return CELL ? e >> 5 : tbl_ix<false>(0u, e >> 6, (e >> 5) & 1u);
 }
 
+// (A cell is read and cleared as one uint64_t while the picks OR into its halves as uint32_t: the
+// accesses of the two types to one cell are always separated by wave_lds_sync(), whose fence is
+// what keeps the compiler from reordering them; tbl[] is 8-byte aligned and a cell's index even.)
+template <bool CELL>
 __device__ __forceinline__ uint64_t tbl_word(const ScatterLds& L, int j, int w) {
-  return ((uint64_t)L.tbl[tbl_ix(j, w, 1)] << 32) | L.tbl[tbl_ix(j, w, 0)];
+  if constexpr (CELL) return *reinterpret_cast<const uint64_t*>(&L.tbl[tbl_ix<true>(j, w, 0)]);
+  return ((uint64_t)L.tbl[tbl_ix<false>(j, w, 1)] << 32) | L.tbl[tbl_ix<false>(j, w, 0)];
 }
 
+template <bool CELL>
 __device__ __forceinline__ void tbl_clear(ScatterLds& L, int j, int w) {
-  L.tbl[tbl_ix(j, w, 0)] = 0u;
-  L.tbl[tbl_ix(j, w, 1)] = 0u;
+  if constexpr (CELL) {
+    *reinterpret_cast<uint64_t*>(&L.tbl[tbl_ix<true>(j, w, 0)]) = 0ull;
+  } else {
+    L.tbl[tbl_ix<false>(j, w, 0)] = 0u;
+    L.tbl[tbl_ix<false>(j, w, 1)] = 0u;
+  }
 }
 
 // Gossip, round r >= 0: every first receipt (v, m) of round r is pushed to k Philox-chosen
@@ -1182,12 +1212,18 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
   const bool all = deg <= k;
   const int w = sl * 64 + lane;
   const bool valid = w < W;
+  constexpr bool CELL = P2PG_NP_CELL64 != 0 && K > 0;  // the table's layout (ScatterLds)
   const uint64_t fam = __ballot(f != 0ull);  // active words of this slice
   const bool anyf = fam != 0ull;
   if (!anyf && !STORE_E) return;
   const uint32_t gv = gidx_s(g, v);
   // the source's folded Philox rounds (philox_pick: only the message varies per draw)
   const PickKey pkey = pick_key((uint32_t)p.round, gv, p.gseed_lo, p.gseed_hi);
+#if P2PG_NP_CMP32
+  // Floyd's bounds for this source, in vector registers across its pick batches (philox.h)
+  uint32_t pjm[K > 0 && K <= 4 ? K : 1];
+  if constexpr (K > 0 && K <= 4) pick_bounds<K>((uint32_t)deg, pjm);
+#endif
 
   // Philox + Floyd for one (word, bit) entry e = word << 6 | bit of this slice, its picks ORed
   // into the LDS table (an empty mask when !ok); CHECK: picks outside this chunk are dropped.
@@ -1195,14 +1231,19 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
     constexpr bool CHECK = decltype(check_v)::value;
     const uint32_t wl = e >> 6, bit = e & 63u;
     const uint32_t mg = p.msg_base + (uint32_t)((sl * 64 + (int)wl) * 64) + bit;
-    uint32_t* const col = &L.tbl[tbl_entry_ix(e)];  // connection 0's (word, half)
+    uint32_t* const col = &L.tbl[tbl_entry_ix<CELL>(e)];  // connection 0's (word, half)
     const uint32_t mb = ok ? 1u << (bit & 31u) : 0u;
     uint32_t pk[K > 0 ? K : 1];
-    if constexpr (K > 0 && K <= 4)
+    if constexpr (K > 0 && K <= 4) {
+#if P2PG_NP_CMP32
+      gossip_picks_kb<K>(pkey, mg, (uint32_t)deg, pjm, pk);
+#else
       gossip_picks_k<K>(pkey, mg, (uint32_t)deg, pk);
-    else
+#endif
+    } else {
       gossip_picks_t<(K > 0 ? K : 1)>((uint32_t)p.round, gv, mg, (uint32_t)deg, p.gseed_lo,
                                       p.gseed_hi, pk);
+    }
 #pragma unroll
     for (int q = 0; q < (K > 0 ? K : 1); ++q) {
       const uint32_t jj = pk[q] - (uint32_t)nb;
@@ -1270,11 +1311,11 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
     if (compact) {
       for (int j0 = 0; j0 < nn; j0 += gper) {
         const int jj = j0 + gl;
-        if (rk && jj < nn) tbl_clear(L, jj, wc);
+        if (rk && jj < nn) tbl_clear<CELL>(L, jj, wc);
       }
     } else {
       for (int j = 0; j < nn; ++j) {
-        tbl_clear(L, j, lane);
+        tbl_clear<CELL>(L, j, lane);
       }
     }
     const uint32_t cnt = (uint32_t)__popcll(f);
@@ -1301,9 +1342,15 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
     // word-major compaction: lane w lists its word's set bits at its exclusive prefix-sum
     // position (one DPP scan; a 32-bit ctz / clear per bit), so every lane gets an equal
     // share of the Philox work; pick_batch reads the list strided (distinct words per batch)
+#if P2PG_NP_SCAN
+    uint32_t incl = 0u;
+    const uint32_t pos0 = direct ? 0u : wave_scan_excl_u32(cnt, incl);
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+#else
     const uint32_t incl = direct ? 0u : wave_scan_u32(cnt);
     const uint32_t total = direct ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     const uint32_t pos0 = incl - cnt;
+#endif
     // a pass lists GLIST - 1 entries; the last list slot takes the entries not written
     constexpr uint32_t CAP = (uint32_t)GLIST - 1u;
     for (uint32_t lb = 0; lb < total; lb += CAP) {
@@ -1326,7 +1373,7 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
           const uint32_t e = L.lst[i];
           const uint32_t wl = e >> 6, bit = e & 63u;
           const uint32_t mg = p.msg_base + (uint32_t)((sl * 64 + (int)wl) * 64) + bit;
-          uint32_t* const col = &L.tbl[tbl_ix(0u, wl, bit >> 5)];
+          uint32_t* const col = &L.tbl[tbl_ix<CELL>(0u, wl, bit >> 5)];
           const uint32_t mb = 1u << (bit & 31u);
           uint32_t pk[16];
           gossip_picks((uint32_t)p.round, gv, mg, (uint32_t)deg, k, p.gseed_lo, p.gseed_hi, pk);
@@ -1353,7 +1400,7 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
       const int jj = j0 + gl;
       const bool ok = rk && jj < nn;
       uint64_t x = 0;
-      if (ok) x = all ? fr : tbl_word(L, jj, wc);
+      if (ok) x = all ? fr : tbl_word<CELL>(L, jj, wc);
       const uint32_t nj = (uint32_t)__builtin_amdgcn_ds_bpermute(
           (nbr0 + (jj < nn ? jj : 0)) << 2, (int)nbr);
       const uint64_t bal = __ballot(ok && x != 0ull);
@@ -1371,7 +1418,7 @@ __device__ __forceinline__ void scatter_row(const DevGraph& g, const DevState& s
     return;
   }
   auto tbl_row = [&](int j) -> uint64_t {
-    return tbl_word(L, j, lane);
+    return tbl_word<CELL>(L, j, lane);
   };
   uint64_t xn = use_tbl && nn > 0 ? tbl_row(0) : 0ull;
   for (int j = 0; j < nn; ++j) {
@@ -1448,9 +1495,14 @@ __device__ __forceinline__ void scatter_wide(const DevGraph& g, const DevState& 
   const PickKey pkey = pick_key((uint32_t)p.round, gv, p.gseed_lo, p.gseed_hi);
   // word-major entry list: lane w's bits at its exclusive prefix of popcounts
   const uint32_t cnt = (uint32_t)__popcll(f);
+#if P2PG_NP_SCAN
+  uint32_t incl;
+  const uint32_t pos0 = wave_scan_excl_u32(cnt, incl);
+#else
   const uint32_t incl = wave_scan_u32(cnt);
-  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
   const uint32_t pos0 = incl - cnt;
+#endif
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
   // lane r: the list position of the first entry of the word of rank r (r < nf; the inactive
   // words write lane 63, which is rank 63 only when every word is active)
   const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(fam >> 32),
