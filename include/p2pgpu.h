@@ -40,6 +40,10 @@
  *   p2pg_message_cost             <- per payload id: the send_to_node calls that carried it
  *                                    (node.py:116) and the packets of it that a receive loop
  *                                    handed on (nodeconnection.py:215)
+ *   p2pg_message_latency /        <- the node_message events that pass the app's dedup
+ *   p2pg_peer_latency                (node.py:334-338, README.md:20), by how many rounds after the
+ *                                    broadcast's own start they happened: per broadcast a
+ *                                    histogram, per peer their sum / number / largest
  *   p2pg_last_error             <- (reference swallows errors via debug_print, node.py:80-83)
  *
  * Conventions: plain C types only; 0 = OK, negative = error (message via p2pg_last_error);
@@ -105,6 +109,19 @@ extern "C" {
                                     rows and a per-message pass over its sends precedes the next
                                     round (the price: DESIGN.md 4g).  Not on a vertex-partitioned
                                     rank, not with snapshots                                     */
+
+#define P2PG_FLAG_LATENCY 128u /* delivery latency on the device: per broadcast a histogram of the
+                                    relative hops (round - start round) of its first receipts
+                                    (p2pg_message_latency), per peer their sum, number and largest
+                                    (p2pg_peer_latency).  Independent of P2PG_FLAG_TALLY and
+                                    P2PG_FLAG_MSG_COST (any combination).  M (bins 8 + 4) + V 16
+                                    bytes of device memory (config 4: 160 MB per-peer, 2 MB of
+                                    histograms at 64 bins), the start rounds as bit planes and,
+                                    without P2PG_FLAG_TALLY, 256 KB of shard scratch per 4096
+                                    messages; every round keeps its whole frontier rows, a column
+                                    count and a per-peer pass follow each round (the price:
+                                    DESIGN.md 4g).  Not on a vertex-partitioned rank, not with
+                                    snapshots                                                    */
 
 typedef struct p2pg_engine p2pg_engine;
 typedef struct p2pg_graph p2pg_graph;
@@ -452,6 +469,31 @@ int p2pg_peer_counters(p2pg_engine* e, uint64_t* sent, uint64_t* received);
  * the counters.  P2PG_ERR_STATE without the flag, before sources are set, between
  * p2pg_step_begin and p2pg_step_end, and on a vertex-partitioned rank.                       */
 int p2pg_message_cost(p2pg_engine* e, uint64_t* sent, uint64_t* received);
+/* ---- delivery latency (P2PG_FLAG_LATENCY): how long delivery took, computed on the device ----
+ * The relative hop of a first receipt of message m in round r -- a node_message event that passes
+ * the app's dedup (node.py:334-338, README.md:20) -- is h = r - start[m]; the origination is the
+ * receipt with h = 0 at the origin and is counted, as in reach.  A receipt is counted at the end
+ * of the round in which it happens, from the round's final frontier: an offline peer's undone
+ * receipt is not counted, a receipt an anti-entropy reply made is counted with the hop of its
+ * arrival round, an expired or muted receipt is counted (it happened), and a later
+ * p2pg_drop_relays or p2pg_update_edges changes nothing (they withdraw relays, not receipts).
+ * Reading needs no final sends and refuses nothing afterwards.
+ * All three: P2PG_ERR_STATE without the flag, before p2pg_set_sources, between p2pg_step_begin /
+ * p2pg_step_end and on a vertex-partitioned rank.  p2pg_reset and p2pg_set_sources[_at] zero the
+ * counters and keep the number of bins.
+ *
+ * The histograms' number of bins, 2..1024 (P2PG_ERR_ARG outside; default 64): the last bin
+ * collects every hop >= bins - 1.  P2PG_ERR_STATE once a round has run (allowed again after
+ * p2pg_reset).                                                                                 */
+int p2pg_set_latency_bins(p2pg_engine* e, int32_t bins);
+/* hist[M][bins], row-major: hist[m][b] = the first receipts of m so far with min(h, bins - 1) == b;
+ * sum_b hist[m][b] == p2pg_message_reach[m].  bins must be the engine's (P2PG_ERR_ARG).       */
+int p2pg_message_latency(p2pg_engine* e, int32_t bins, uint64_t* hist);
+/* Per peer, exact and independent of bins ([V]; any pointer may be NULL):
+ *   hop_sum[v]   sum of h over v's first receipts so far
+ *   receipts[v]  their number; sum_v receipts[v] == sum_m reach[m]
+ *   max_hop[v]   the largest h, -1 with no receipt                                          */
+int p2pg_peer_latency(p2pg_engine* e, uint64_t* hop_sum, uint32_t* receipts, int32_t* max_hop);
 /* Summed device time per kernel class since the last reset (needs P2PG_FLAG_TIMING):
  * 0 seed (origination, in round 0 and later; the hop-limit passes of expiry rounds; the relay-policy
  * and downtime passes; the two anti-entropy passes of arrival rounds, k_pull_gather and

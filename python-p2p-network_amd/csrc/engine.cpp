@@ -49,6 +49,7 @@
 #include "anti_entropy.h"
 #include "downtime.h"
 #include "internal.h"
+#include "latency.h"
 #include "philox.h"
 #include "round_plan.h"
 
@@ -208,6 +209,17 @@ struct p2pg_engine {
   unsigned long long* d_csent = nullptr;
   unsigned long long* d_crecv = nullptr;
   unsigned long long* d_cscratch = nullptr;
+  // delivery latency (P2PG_FLAG_LATENCY; relay_latency.hip): per message the histogram of relative
+  // hops [M][lat_bins], per peer hop sum / receipts / largest hop [V]; the device copy of h_start
+  // [M] and its bit-sliced planes [lat_B][W] (latency.h), kept equal to h_start wherever it changes
+  // (upload_latency).  The frontier count's shards are d_tscratch, shared with the tallies.
+  int32_t lat_bins = latency::BINS_DEFAULT;
+  unsigned long long* d_lhist = nullptr;
+  PeerLat* d_lpeer = nullptr;
+  int32_t* d_lstart = nullptr;
+  uint64_t* d_lplanes = nullptr;
+  int32_t lat_B = 0;            // planes in use (0: every start is 0)
+  int64_t lat_planes_cap = 0;   // words allocated at d_lplanes
   int32_t tally_pending = -1;   // the round whose sends the peer / cost counters do not hold yet: they
                                 // are final (drops, removed connections) only at the next round's
                                 // start, in p2pg_update_edges or when the counters are read
@@ -329,6 +341,12 @@ void free_state(p2pg_engine* e) {
   dfree(e->d_csent);
   dfree(e->d_crecv);
   dfree(e->d_cscratch);
+  dfree(e->d_lhist);
+  dfree(e->d_lpeer);
+  dfree(e->d_lstart);
+  dfree(e->d_lplanes);
+  e->lat_planes_cap = 0;
+  e->lat_B = 0;
   DevState& s = e->st;
   dfree(s.seen);
   if (e->seen_spare) {
@@ -698,7 +716,45 @@ bool deferred_on(const p2pg_engine* e) { return tally_on(e) || cost_on(e); }
 // Does a round of this engine need its frontier rows whole (no skipped / partial rows, no
 // batched decay rounds)?
 // (a relay policy reads and rewrites the rows of every round: relay_policy.hip)
-bool frontier_needed(const p2pg_engine* e) { return count_lost_on(e) || deferred_on(e) || e->pol_on; }
+// Delivery latency (P2PG_FLAG_LATENCY): every round keeps its whole frontier rows, which the two
+// latency passes read at the round's end.  Nothing is deferred: receipts are final then.
+bool latency_on(const p2pg_engine* e) { return (e->cfg.flags & P2PG_FLAG_LATENCY) != 0; }
+bool frontier_needed(const p2pg_engine* e) {
+  return count_lost_on(e) || deferred_on(e) || latency_on(e) || e->pol_on;
+}
+
+// The device copy of the start rounds and their bit-sliced planes from h_start (the caller has
+// synchronised the stream: upload_schedule).  The planes grow when a later start needs more bits.
+int upload_latency(p2pg_engine* e) {
+  const int32_t M = e->M, W = e->W;
+  const int B = latency::plane_bits(latency::max_start(M, e->h_start.data()));
+  HIPCHK(e, hipMemcpy(e->d_lstart, e->h_start.data(), sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice));
+  e->lat_B = B;
+  if (!B) return P2PG_OK;
+  const int64_t words = (int64_t)B * W;
+  if (words > e->lat_planes_cap) {
+    dfree(e->d_lplanes);
+    e->lat_planes_cap = 0;
+    HIPCHK(e, hipMalloc((void**)&e->d_lplanes, sizeof(uint64_t) * (size_t)words));
+    e->lat_planes_cap = words;
+  }
+  std::vector<uint64_t> planes((size_t)words);
+  latency::build_start_planes(M, W, e->h_start.data(), B, planes.data());
+  HIPCHK(e, hipMemcpy(e->d_lplanes, planes.data(), sizeof(uint64_t) * (size_t)words, hipMemcpyHostToDevice));
+  return P2PG_OK;
+}
+
+// The histogram plane [M][lat_bins], zeroed (alloc_state, p2pg_set_latency_bins).
+int alloc_latency_hist(p2pg_engine* e) {
+  dfree(e->d_lhist);
+  const size_t hb = sizeof(unsigned long long) * (size_t)e->M * (size_t)e->lat_bins;
+  const hipError_t r = hipMalloc((void**)&e->d_lhist, hb ? hb : 8);
+  if (r != hipSuccess)
+    return fail(e, r == hipErrorOutOfMemory ? P2PG_ERR_NOMEM : P2PG_ERR_HIP,
+                std::string("hipMalloc (latency histograms): ") + hipGetErrorString(r));
+  HIPCHK(e, hipMemsetAsync(e->d_lhist, 0, hb, e->stream));
+  return P2PG_OK;
+}
 
 // Enqueue the peer counters and / or the per-message cost of the pending round (its sends are
 // final now): the sends leave on
@@ -838,6 +894,23 @@ int alloc_state(p2pg_engine* e) {
       return fail(e, P2PG_ERR_HIP, std::string("alloc_state (message cost): ") + hipGetErrorString(zr));
     }
   }
+  if (latency_on(e)) {  // M * (bins * 8 + 4) + V * 16 bytes; the planes follow the schedule (upload_latency)
+    if ((rc = alloc_latency_hist(e))) {
+      free_state(e);
+      return rc;
+    }
+    if ((rc = A((void**)&e->d_lstart, sizeof(int32_t) * (size_t)e->M))) return rc;
+    if ((rc = A((void**)&e->d_lpeer, sizeof(PeerLat) * (size_t)e->V))) return rc;
+    if (!e->d_tscratch) {  // (with P2PG_FLAG_TALLY the two folds share the tally's shards)
+      const size_t sb = sizeof(unsigned long long) * (size_t)tally_scratch_words(e->W);
+      if ((rc = A((void**)&e->d_tscratch, sb))) return rc;
+      const hipError_t zr = hipMemsetAsync(e->d_tscratch, 0, sb, e->stream);
+      if (zr != hipSuccess) {
+        free_state(e);
+        return fail(e, P2PG_ERR_HIP, std::string("alloc_state (latency): ") + hipGetErrorString(zr));
+      }
+    }
+  }
 #ifdef P2PG_PROF
   if ((rc = A((void**)&s.prof, sizeof(unsigned long long) * 16))) return rc;
   HIPCHK(e, hipMemset(s.prof, 0, sizeof(unsigned long long) * 16));
@@ -864,6 +937,9 @@ int p2pg_create(const p2pg_config* cfg, p2pg_engine** out) {
                                        "(P2PG_FLAG_LOCAL_GRAPH): ghost rows would be counted on two ranks");
   if ((cfg->flags & P2PG_FLAG_MSG_COST) && (cfg->flags & P2PG_FLAG_LOCAL_GRAPH))
     return fail(nullptr, P2PG_ERR_ARG, "create: P2PG_FLAG_MSG_COST is not available on a vertex-partitioned rank "
+                                       "(P2PG_FLAG_LOCAL_GRAPH): ghost rows would be counted on two ranks");
+  if ((cfg->flags & P2PG_FLAG_LATENCY) && (cfg->flags & P2PG_FLAG_LOCAL_GRAPH))
+    return fail(nullptr, P2PG_ERR_ARG, "create: P2PG_FLAG_LATENCY is not available on a vertex-partitioned rank "
                                        "(P2PG_FLAG_LOCAL_GRAPH): ghost rows would be counted on two ranks");
   int ndev = 0;
   hipError_t r = hipGetDeviceCount(&ndev);
@@ -1120,7 +1196,7 @@ int upload_schedule(p2pg_engine* e) {
     HIPCHK(e, hipMemcpy(e->d_sched_msg, msg.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(e->d_sched_grp, grp.data(), sizeof(int64_t) * grp.size(), hipMemcpyHostToDevice));
   }
-  return P2PG_OK;
+  return latency_on(e) ? upload_latency(e) : P2PG_OK;
 }
 
 // The originations of round r > 0, or nullptr.
@@ -1717,6 +1793,10 @@ int p2pg_reset(p2pg_engine* e) {
     HIPCHK(e, hipMemsetAsync(e->d_csent, 0, sizeof(unsigned long long) * (size_t)e->M, e->stream));
     HIPCHK(e, hipMemsetAsync(e->d_crecv, 0, sizeof(unsigned long long) * (size_t)e->M, e->stream));
   }
+  if (latency_on(e)) {
+    HIPCHK(e, hipMemsetAsync(e->d_lhist, 0, sizeof(unsigned long long) * (size_t)e->M * (size_t)e->lat_bins, e->stream));
+    HIPCHK(e, hipMemsetAsync(e->d_lpeer, 0, sizeof(PeerLat) * (size_t)e->V, e->stream));
+  }
   e->tally_pending = -1;
   e->tally_read_at = -1;
   e->exp_pending = e->exp_final = -1;  // (the hop limits themselves stay and are replayed)
@@ -1999,7 +2079,21 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     if (r != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("step (exchange pack): ") + hipGetErrorString(r));
     e->auto_round = e->round;
   }
-  if (tally_on(e)) {
+  if (latency_on(e)) {
+    // this round's first receipts by relative hop: one column count of its frontier rows, whose
+    // shards the latency fold bins per message -- and, on a tally engine, the tally's fold reads
+    // next and leaves zero -- then the per-peer pass over the same rows.  Stream order only.
+    hipError_t x = launch_frontier_count(s.F[e->round & 1], s.A[e->round & 1], e->V, e->W, e->d_tscratch, e->stream);
+    if (x == hipSuccess)
+      x = launch_latency_fold(e->d_tscratch, e->W, e->M, e->round, e->d_lstart, e->lat_bins, e->d_lhist, !tally_on(e),
+                              e->stream);
+    if (x == hipSuccess && tally_on(e))
+      x = launch_tally_fold(e->d_tscratch, e->W, e->M, e->round, nullptr, e->d_treach, e->d_thop, e->d_tlast,
+                            e->stream);
+    if (x == hipSuccess)
+      x = launch_peer_latency(s, e->V, e->round, e->lat_B ? e->d_lplanes : nullptr, e->lat_B, e->d_lpeer, e->stream);
+    if (x != hipSuccess) return fail(e, P2PG_ERR_HIP, std::string("step (delivery latency): ") + hipGetErrorString(x));
+  } else if (tally_on(e)) {
     // this round's first receipts per message: column counts of its frontier rows (whole on a
     // tally engine); its sends wait for the next boundary (flush_peer_tally)
     const hipError_t x = launch_column_count(s.F[e->round & 1], s.A[e->round & 1], e->V, e->W, e->M, e->round,
@@ -2590,8 +2684,71 @@ int p2pg_message_cost(p2pg_engine* e, uint64_t* sent, uint64_t* received) {
   return P2PG_OK;
 }
 
+// Shared preconditions of the latency calls: the flag, sources set, between rounds, one rank.
+static int latency_state(p2pg_engine* e, const char* what) {
+  const std::string w(what);
+  if (!e) return fail(e, P2PG_ERR_ARG, w + ": no engine");
+  if (!latency_on(e)) return fail(e, P2PG_ERR_STATE, w + ": needs P2PG_FLAG_LATENCY");
+  if (!e->have_state) return fail(e, P2PG_ERR_STATE, w + ": no sources set");
+  if (e->begun) return fail(e, P2PG_ERR_STATE, w + ": a round has begun (step_begin)");
+  if (e->d_gid || (e->cfg.flags & P2PG_FLAG_LOCAL_GRAPH))
+    return fail(e, P2PG_ERR_STATE, w + ": not on a vertex-partitioned rank");
+  return P2PG_OK;
+}
+
+int p2pg_set_latency_bins(p2pg_engine* e, int32_t bins) {
+  int rc = latency_state(e, "set_latency_bins");
+  if (rc) return rc;
+  if (bins < latency::BINS_MIN || bins > latency::BINS_MAX)
+    return fail(e, P2PG_ERR_ARG, "set_latency_bins: bins must lie in [2, 1024]");
+  if (e->round > 0)
+    return fail(e, P2PG_ERR_STATE, "set_latency_bins: a round has run (set the bins before round 0, or after p2pg_reset)");
+  if (bins == e->lat_bins) return P2PG_OK;
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  HIPCHK(e, hipStreamSynchronize(e->stream));  // (a reset's zeroing of the old plane may be queued)
+  const int32_t old = e->lat_bins;
+  e->lat_bins = bins;
+  if ((rc = alloc_latency_hist(e))) {
+    e->lat_bins = old;
+    const int rc2 = alloc_latency_hist(e);
+    return rc2 ? rc2 : rc;
+  }
+  return P2PG_OK;
+}
+
+int p2pg_message_latency(p2pg_engine* e, int32_t bins, uint64_t* hist) {
+  int rc = latency_state(e, "message_latency");
+  if (rc) return rc;
+  if (!hist) return fail(e, P2PG_ERR_ARG, "message_latency: no output array");
+  if (bins != e->lat_bins)
+    return fail(e, P2PG_ERR_ARG, "message_latency: bins differs from the engine's (" + std::to_string(e->lat_bins) + ")");
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipMemcpy(hist, e->d_lhist, sizeof(unsigned long long) * (size_t)e->M * (size_t)bins, hipMemcpyDeviceToHost));
+  return P2PG_OK;
+}
+
+int p2pg_peer_latency(p2pg_engine* e, uint64_t* hop_sum, uint32_t* receipts, int32_t* max_hop) {
+  int rc = latency_state(e, "peer_latency");
+  if (rc) return rc;
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (!hop_sum && !receipts && !max_hop) return P2PG_OK;
+  std::vector<PeerLat> h((size_t)e->V);
+  HIPCHK(e, hipMemcpy(h.data(), e->d_lpeer, sizeof(PeerLat) * (size_t)e->V, hipMemcpyDeviceToHost));
+  for (int64_t v = 0; v < e->V; ++v) {
+    if (hop_sum) hop_sum[v] = h[v].hop_sum;
+    if (receipts) receipts[v] = h[v].receipts;
+    if (max_hop) max_hop[v] = (int32_t)h[v].max1 - 1;
+  }
+  return P2PG_OK;
+}
+
 int p2pg_set_global_ids(p2pg_engine* e, const int32_t* gid) {
   if (!e || !e->d_rowptr) return fail(e, P2PG_ERR_STATE, "set_global_ids: load a graph first");
+  if (latency_on(e))
+    return fail(e, P2PG_ERR_STATE, "set_global_ids: a P2PG_FLAG_LATENCY engine cannot be a vertex-partitioned "
+                                   "rank (ghost rows would be counted on two ranks)");
   if (tally_on(e))
     return fail(e, P2PG_ERR_STATE, "set_global_ids: a P2PG_FLAG_TALLY engine cannot be a vertex-partitioned "
                                    "rank (ghost rows would be counted on two ranks)");
@@ -3076,6 +3233,8 @@ int p2pg_snapshot(p2pg_engine* e, void* buf, int64_t cap) {
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold run tallies (P2PG_FLAG_TALLY)");
   if (cost_on(e))
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold the per-message cost (P2PG_FLAG_MSG_COST)");
+  if (latency_on(e))
+    return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold the delivery latency (P2PG_FLAG_LATENCY)");
   if (e->late)
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold start rounds other than 0 "
                                    "(p2pg_set_sources_at / p2pg_originate)");
@@ -3152,6 +3311,8 @@ int p2pg_restore(p2pg_engine* e, const void* buf, int64_t size) {
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold run tallies (P2PG_FLAG_TALLY)");
   if (cost_on(e))
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold the per-message cost (P2PG_FLAG_MSG_COST)");
+  if (latency_on(e))
+    return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold the delivery latency (P2PG_FLAG_LATENCY)");
   if (e->late)
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold start rounds other than 0 "
                                    "(p2pg_set_sources_at / p2pg_originate)");

@@ -695,27 +695,43 @@ hipError_t launch_msg_cost(const DevGraph& gs, const DevGraph& gp, const DevStat
 
 int64_t tally_scratch_words(int32_t W) { return (int64_t)TALLY_SHARDS * ((W + 63) / 64) * 4096; }
 
+hipError_t launch_frontier_count(const uint64_t* plane, const uint32_t* A, int64_t V, int32_t W,
+                                 unsigned long long* scratch, hipStream_t s) {
+  if (V <= 0 || W <= 0) return hipSuccess;
+  const int nsl = (W + 63) / 64;
+  const int64_t nbt = (((V + 31) >> 5) + WPB - 1) / WPB;
+  hipLaunchKernelGGL(k_colcount<true>, dim3(grid_tasks(nbt * nsl * WPB)), dim3(256), 0, s, plane, A, V, W,
+                     scratch, TALLY_SHARDS);
+  return hipGetLastError();
+}
+
+hipError_t launch_tally_fold(unsigned long long* scratch, int32_t W, int32_t M, int32_t round,
+                             unsigned long long* reach_out, unsigned long long* reach,
+                             unsigned long long* hop_sum, int32_t* last_hop, hipStream_t s) {
+  if (W <= 0) return hipSuccess;
+  const int64_t n = (int64_t)((W + 63) / 64) * 4096;
+  hipLaunchKernelGGL(k_tally_fold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scratch, TALLY_SHARDS, n,
+                     M, round, reach_out, reach, hop_sum, last_hop);
+  return hipGetLastError();
+}
+
 hipError_t launch_column_count(const uint64_t* plane, const uint32_t* A, int64_t V, int32_t W, int32_t M,
                                int32_t round, unsigned long long* scratch, unsigned long long* reach_out,
                                unsigned long long* reach, unsigned long long* hop_sum, int32_t* last_hop,
                                hipStream_t s) {
   if (V <= 0 || W <= 0) return hipSuccess;
-  const int nsl = (W + 63) / 64;
-  const int64_t n = (int64_t)nsl * 4096;
+  hipError_t r;
   if (A) {
-    const int64_t nbt = (((V + 31) >> 5) + WPB - 1) / WPB;
-    hipLaunchKernelGGL(k_colcount<true>, dim3(grid_tasks(nbt * nsl * WPB)), dim3(256), 0, s, plane, A, V, W,
-                       scratch, TALLY_SHARDS);
+    r = launch_frontier_count(plane, A, V, W, scratch, s);
   } else {
+    const int nsl = (W + 63) / 64;
     const int64_t nbt = ((V + TALLY_ROWS - 1) / TALLY_ROWS + WPB - 1) / WPB;
     hipLaunchKernelGGL(k_colcount<false>, dim3(grid_tasks(nbt * nsl * WPB)), dim3(256), 0, s, plane, A, V, W,
                        scratch, TALLY_SHARDS);
+    r = hipGetLastError();
   }
-  hipError_t r = hipGetLastError();
   if (r != hipSuccess) return r;
-  hipLaunchKernelGGL(k_tally_fold, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scratch, TALLY_SHARDS, n,
-                     M, round, reach_out, reach, hop_sum, last_hop);
-  return hipGetLastError();
+  return launch_tally_fold(scratch, W, M, round, reach_out, reach, hop_sum, last_hop, s);
 }
 
 hipError_t launch_peer_tally(const DevGraph& gs, const DevGraph& gp, const DevState& st, const RoundParams& p,

@@ -11,11 +11,11 @@ The HIP engine is reached through ctypes (``_lib``); there is no CPU fallback.
 from ._lib import P2PGError, LIB_PATH
 from .graph import PeerGraph, make_sources
 from .network import (GraphNetwork, RoundStats, Deliveries, MessageTally, PeerCounters,
-                      MessageCost, churn_threshold)
+                      MessageCost, PeerLatency, churn_threshold)
 from .partition import VertexPartition, PartitionedNetwork, TorchTransport
 from .compat import SimNode, SimConnection, CompatNetwork
 from . import wire
 
 __all__ = ["P2PGError", "LIB_PATH", "PeerGraph", "make_sources", "GraphNetwork", "RoundStats",
-           "Deliveries", "MessageTally", "PeerCounters", "MessageCost", "churn_threshold", "VertexPartition", "PartitionedNetwork", "TorchTransport",
+           "Deliveries", "MessageTally", "PeerCounters", "MessageCost", "PeerLatency", "churn_threshold", "VertexPartition", "PartitionedNetwork", "TorchTransport",
            "SimNode", "SimConnection", "CompatNetwork", "wire"]

@@ -22,6 +22,7 @@ FLAG_LOCAL_GRAPH = 8
 FLAG_RECEIVED = 16
 FLAG_TALLY = 32
 FLAG_MSG_COST = 64
+FLAG_LATENCY = 128
 
 # graph kinds of p2pg_graph_generate
 GRAPH_RANDOM_REGULAR = 0
@@ -122,6 +123,9 @@ SIGNATURES = {
     "p2pg_message_tally": (ctypes.c_int, [_P, _P, _P, _P]),
     "p2pg_peer_counters": (ctypes.c_int, [_P, _P, _P]),
     "p2pg_message_cost": (ctypes.c_int, [_P, _P, _P]),
+    "p2pg_set_latency_bins": (ctypes.c_int, [_P, _I32]),
+    "p2pg_message_latency": (ctypes.c_int, [_P, _I32, _P]),
+    "p2pg_peer_latency": (ctypes.c_int, [_P, _P, _P, _P]),
     "p2pg_kernel_times": (ctypes.c_int, [_P, _P, _P]),
     "p2pg_set_timed_classes": (ctypes.c_int, [_P, ctypes.c_uint32]),
     "p2pg_set_global_ids": (ctypes.c_int, [_P, _P]),

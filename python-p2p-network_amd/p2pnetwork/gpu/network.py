@@ -108,6 +108,20 @@ PeerCounters = namedtuple("PeerCounters", "sent received")
 # p2pg_message_cost
 MessageCost = namedtuple("MessageCost", "sent received")
 
+
+class PeerLatency(namedtuple("PeerLatency", "hop_sum receipts max_hop")):
+    """Delivery latency per peer (GraphNetwork(latency=True)), [V]: uint64 hop_sum (sum over the
+    peer's first receipts of their relative hop, round - start round of the broadcast), uint32
+    receipts (their number), int32 max_hop (the largest, -1 = no receipt) -- p2pg_peer_latency"""
+    __slots__ = ()
+
+    def mean(self):
+        """float64 [V]: hop_sum / receipts, NaN for a peer without a receipt."""
+        out = np.full(len(self.receipts), np.nan)
+        ok = self.receipts > 0
+        out[ok] = self.hop_sum[ok].astype(np.float64) / self.receipts[ok].astype(np.float64)
+        return out
+
 # index of SnapHeader.total_relays in the snapshot header viewed as uint64 words (engine.cpp:
 # magic 0, version/mode 1, V 2, nnz 3, M/W 4, fanout/round 5, flags/thr 6, base/done 7,
 # consume/has_next 8, gossip_seed 9, churn_seed 10, graph_hash 11, src_hash 12, total_relays 13)
@@ -141,7 +155,7 @@ class GraphNetwork:
     def __init__(self, graph, mode="flood", fanout=3, gossip_seed=0x5EED, churn=0.0,
                  churn_threshold_value=None, churn_seed=0xC0FFEE, record=False, timing=False,
                  device=0, msg_id_base=0, callback=None, autostop=True, local_graph=False,
-                 count_received=False, tally=False, cost=False):
+                 count_received=False, tally=False, cost=False, latency=False, latency_bins=64):
         if not isinstance(graph, PeerGraph):
             raise TypeError("graph must be a PeerGraph")
         if mode not in ("flood", "gossip"):
@@ -151,6 +165,11 @@ class GraphNetwork:
         self.fanout = int(fanout)
         self.record = bool(record)
         self.callback = callback
+        self.latency = bool(latency)
+        self.latency_bins = int(latency_bins)
+        if self.latency and not 2 <= self.latency_bins <= 1024:
+            raise ValueError("latency_bins must lie in [2, 1024]")
+        self._engine_bins = 64       # the engine's number of histogram bins (its default)
         cfg = _lib.Config()
         cfg.mode = _lib.MODE_FLOOD if mode == "flood" else _lib.MODE_GOSSIP
         cfg.fanout = self.fanout
@@ -164,7 +183,8 @@ class GraphNetwork:
                      | (_lib.FLAG_LOCAL_GRAPH if local_graph else 0)
                      | (_lib.FLAG_RECEIVED if count_received else 0)
                      | (_lib.FLAG_TALLY if tally else 0)
-                     | (_lib.FLAG_MSG_COST if cost else 0))
+                     | (_lib.FLAG_MSG_COST if cost else 0)
+                     | (_lib.FLAG_LATENCY if latency else 0))
         cfg.device = int(device)
         self.config = cfg
         L = _lib.lib()
@@ -246,6 +266,8 @@ class GraphNetwork:
             self._check(_lib.lib().p2pg_set_sources_at(self._h, len(src), _lib.ptr(src), _lib.ptr(start)))
         self.sources = src
         self.start_rounds = start
+        if self.latency and self.latency_bins != self._engine_bins:  # (the engine keeps it from here on)
+            self.set_latency_bins(self.latency_bins)
         self.ttl = np.full(len(src), -1, dtype=np.int32)  # (new sources carry no hop limits)
         self.rounds = []
         self.message_count_send = 0
@@ -631,7 +653,8 @@ class GraphNetwork:
         """MessageTally(reach, hop_sum, last_hop) per broadcast, accumulated from every round's
         first receipts; needs tally=True (p2pg_message_tally).  Hops are absolute round indices:
         for a broadcast that started late, the mean hop counted from its own start is
-        ``hop_sum / reach - start_rounds`` and its last hop ``last_hop - start_rounds``."""
+        ``hop_sum / reach - start_rounds`` and its last hop ``last_hop - start_rounds``
+        (``message_latency()`` with latency=True gives the whole distribution from the start)."""
         reach = np.zeros(self.M, dtype=np.uint64)
         hop_sum = np.zeros(self.M, dtype=np.uint64)
         last_hop = np.zeros(self.M, dtype=np.int32)
@@ -658,6 +681,61 @@ class GraphNetwork:
         received = np.zeros(self.M, dtype=np.uint64)
         self._check(_lib.lib().p2pg_message_cost(self._h, _lib.ptr(sent), _lib.ptr(received)))
         return MessageCost(sent, received)
+
+    # -- delivery latency, computed on the device ---------------------------------------------
+    def set_latency_bins(self, bins):
+        """The histograms' number of bins, 2..1024, before round 0 runs or after ``reset``
+        (p2pg_set_latency_bins); needs latency=True and sources."""
+        self._check(_lib.lib().p2pg_set_latency_bins(self._h, int(bins)))
+        self.latency_bins = self._engine_bins = int(bins)
+
+    def message_latency(self):
+        """uint64 [M, bins]: per broadcast the histogram of its first receipts by relative hop
+        (round - start round; the origination is hop 0), the last bin collecting every hop >=
+        bins - 1; needs latency=True (p2pg_message_latency).  Rows sum to ``message_reach()``."""
+        bins = self._engine_bins
+        out = np.zeros((self.M, bins), dtype=np.uint64)
+        self._check(_lib.lib().p2pg_message_latency(self._h, bins, _lib.ptr(out)))
+        return out
+
+    def peer_latency(self):
+        """PeerLatency(hop_sum, receipts, max_hop) per peer, exact whatever the number of bins;
+        needs latency=True (p2pg_peer_latency).  ``.mean()`` is the peer's mean relative hop."""
+        hop_sum = np.zeros(self.graph.V, dtype=np.uint64)
+        receipts = np.zeros(self.graph.V, dtype=np.uint32)
+        max_hop = np.zeros(self.graph.V, dtype=np.int32)
+        self._check(_lib.lib().p2pg_peer_latency(self._h, _lib.ptr(hop_sum), _lib.ptr(receipts),
+                                                 _lib.ptr(max_hop)))
+        return PeerLatency(hop_sum, receipts, max_hop)
+
+    def coverage_curve(self, of="reach"):
+        """float64 [M, bins]: the share delivered within b rounds of the broadcast's start --
+        ``cumsum(message_latency(), axis=1)`` over the broadcast's final reach (``of="reach"``) or
+        over the number of peers (``of="peers"``).  NaN for a broadcast with reach 0 (an
+        unscheduled one).  The last column includes the clamped receipts.  Host arithmetic."""
+        if of not in ("reach", "peers"):
+            raise ValueError("of must be 'reach' or 'peers'")
+        cum = np.cumsum(self.message_latency(), axis=1, dtype=np.uint64)
+        reach = cum[:, -1].astype(np.float64)
+        den = reach if of == "reach" else np.full(self.M, float(self.graph.V))
+        out = np.full(cum.shape, np.nan)
+        ok = reach > 0
+        out[ok] = cum[ok].astype(np.float64) / den[ok, None]
+        return out
+
+    def latency_percentile(self, q):
+        """int32 [M]: the smallest relative hop b by which at least ceil(q * reach) of the
+        broadcast's first receipts had happened, 0 < q <= 1 (q = 0.5: the median rounds to
+        delivery); -1 for a broadcast with reach 0.  A result of ``bins - 1`` is a lower bound:
+        that bin holds every later receipt as well.  Host arithmetic on ``message_latency()``."""
+        if not 0.0 < q <= 1.0:
+            raise ValueError("q must lie in (0, 1]")
+        cum = np.cumsum(self.message_latency(), axis=1, dtype=np.uint64)
+        reach = cum[:, -1]
+        need = np.ceil(q * reach.astype(np.float64)).astype(np.uint64)
+        out = (cum < need[:, None]).sum(axis=1).astype(np.int32)
+        out[reach == 0] = -1
+        return out
 
     def message_redundancy(self):
         """float64 [M]: the relative message redundancy of each broadcast, sent / (reach - 1) - 1
