@@ -204,6 +204,10 @@ int p2pg_relay_muted(uint32_t round, uint32_t peer, uint32_t msg, uint32_t thr, 
 /* 1 iff a peer with the downtime interval [from, until) is offline in round `round`
  * (p2pg_set_downtime; from = -1: never).                                                    */
 int p2pg_peer_offline(int32_t round, int32_t from, int32_t until);
+/* 1 iff a connection between a peer of side_a and a peer of side_b is cut in round `round` under
+ * the window [cut_from, cut_until) (p2pg_set_netsplit): side_a != side_b and cut_from <= round <
+ * cut_until.                                                                                 */
+int p2pg_link_cut(int32_t round, int32_t side_a, int32_t side_b, int32_t cut_from, int32_t cut_until);
 /* The slot, in its ascending connection list of length deg >= 1, of the connection `peer` sends its
  * anti-entropy request of round `round` to under the key `seed` (p2pg_set_anti_entropy):
  * lemire32(philox4x32_10((round, peer, 0, 'AEP'), seed).x, deg).  -1 for deg = 0.            */
@@ -331,6 +335,50 @@ int p2pg_set_relay_policy(p2pg_engine* e, int64_t V, const uint32_t* thr, uint64
  * A round in which somebody is offline takes the unfused schedule (receive pass, the undo of the
  * offline peers' receipts, push); every other round is planned exactly as without the call. */
 int p2pg_set_downtime(p2pg_engine* e, int64_t V, const int32_t* from, const int32_t* until);
+/* Network partition: a netsplit window that heals.  Every peer has a side, side[v] >= 0, and there
+ * is one window of rounds [cut_from, cut_until).  Connection {a, b} is cut in round t iff side[a] !=
+ * side[b] and cut_from <= t < cut_until (p2pg_link_cut).  Peers keep their connections and have no
+ * failure detector: they go on sending over a cut connection, gossip picks are unchanged and a pick
+ * may be wasted on a cut connection.  On the reference harness this is one more term in
+ * dropped(a, b): `or (side[a] != side[b] and cut_from <= round + 1 < cut_until)`.
+ *  1. A send made in round r from v to u is lost iff it was lost before (churn, or a receiver that
+ *     is offline in r + 1) or {v, u} is cut in round r + 1, the round it would arrive in.  Its sender
+ *     still counts it (round r's relays, sent[v], p2pg_message_cost sent, p2pg_get_sends with lost =
+ *     1); it is no arrival (round r + 1's received, received[u], p2pg_message_cost received) and
+ *     sets no seen bit.  u may still get the message later from another copy: an ordinary first
+ *     receipt of that later round, with that round's hop and that round's lowest-id sender whose
+ *     copy arrived as parent.
+ *  2. Originations are not sends: a message may start on any side in any round.
+ *  3. Anti-entropy packets are sends: a request of round r is lost as well if {u, p} is cut in
+ *     r + 1, a reply of round r + 1 if the connection is cut in r + 2 (requests_lost /
+ *     replies_lost of p2pg_pull_stats).  A flood that saturated its side before the heal never
+ *     crosses afterwards -- a peer sends only on a first receipt -- so only the pull repair carries
+ *     its messages across.
+ *  4. Every receipt counter follows from the receipts that happened.  `received` is exact iff
+ *     P2PG_FLAG_RECEIVED is set; without it a round r with cut_from <= r < cut_until reports the
+ *     sends of round r - 1 and received_exact = 0.  p2pg_peer_counters and p2pg_message_cost are
+ *     exact either way.  A flood cut round receives by the cut pull (touched_words 0, push_form
+ *     P2PG_PUSH_NONE as in every flood round).  A gossip round whose sends arrive in a cut round
+ *     (cut_from - 1 <= r <= cut_until - 2) receives and pushes in separate passes with whole
+ *     frontier rows and pushes by row atomics: push_form P2PG_PUSH_ATOMIC, scatter_words = its
+ *     sends that were not lost to churn or the cut (one per (sender, message, pick), or per (sender,
+ *     word, connection) for a sender with deg <= k: an upper bound of the distinct masks other
+ *     rounds report), and the next round's touched_words counts what that push touched.
+ *  5. It composes with flood and gossip, churn, start rounds and p2pg_originate, peer downtime,
+ *     anti-entropy, the three tallies, the records, the delivery stream and p2pg_get_sends, under
+ *     p2pg_step and p2pg_run (which batches no round at or before the last cut round).  p2pg_reset
+ *     and p2pg_set_sources[_at] keep the setting, p2pg_load_csr clears it.  side = NULL, no
+ *     connection between two sides (all sides equal), or cut_until <= cut_from (both >= 0) removes
+ *     it: the engine then launches exactly what it launched before.
+ *  6. P2PG_ERR_STATE, in either call order, a rejected call changing nothing: together with a
+ *     finite hop limit, a relay policy, p2pg_drop_relays or p2pg_update_edges (their held-back pushes
+ *     and rebuilt rows would each need the cut as well), p2pg_snapshot / p2pg_restore, on a
+ *     vertex-partitioned rank (and p2pg_set_global_ids once a netsplit is set), between
+ *     p2pg_step_begin / p2pg_step_end, and once a round has run (allowed again after p2pg_reset).
+ *     P2PG_ERR_ARG: another V, a negative side, cut_from < 0 or cut_until < 0.
+ * Rounds outside the window are planned exactly as without the call; the fused rounds come back
+ * after the heal. */
+int p2pg_set_netsplit(p2pg_engine* e, int64_t V, const int32_t* side, int32_t cut_from, int32_t cut_until);
 /* Anti-entropy: periodic pull repair, the other half of epidemic broadcast.  An exchange happens in
  * every request round r with first <= r <= last and (r - first) % period == 0 and takes three
  * rounds (the reference app: a request queue on the dedup relay's Node, the harness's round being

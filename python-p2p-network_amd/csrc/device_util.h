@@ -10,6 +10,7 @@
 
 #include "downtime.h"
 #include "internal.h"
+#include "netsplit.h"
 #include "philox.h"
 
 namespace p2pg {
@@ -123,18 +124,26 @@ __device__ __forceinline__ uint32_t gidx(const DevGraph& g, int64_t x) {
   return g.gid ? (uint32_t)g.gid[x] : (uint32_t)x;
 }
 
+// Is the connection {a, b} cut in round t (p2pg_set_netsplit, netsplit.h)?  False on an engine
+// without a netsplit (a null side pointer).
+__device__ __forceinline__ bool link_cut(const Netsplit& ns, int32_t t, int64_t a, int64_t b) {
+  return ns.side && netsplit::link_cut(t, ns.side[a], ns.side[b], ns.from, ns.until);
+}
+
 // Does the send of round p.round from v to u over slot `slot` of gs never arrive?  (The sends
 // stream, the lost-send count and the peer tallies: relay_sends.hip, relay_tally.hip.)  The
 // connection was removed before the messages arrived, churn dropped the send, or -- peer downtime,
-// d.from set -- the receiver is offline in round p.round + 1 (downtime.h).  An engine without a
-// downtime passes null pointers and runs the first two tests only.
-__device__ __forceinline__ bool send_lost(const DevGraph& gs, const RoundParams& p, const Downtime& d, int64_t v,
-                                          int32_t u, int64_t slot) {
+// d.from set -- the receiver is offline in round p.round + 1 (downtime.h), or -- a netsplit, ns.side
+// set -- the connection is cut in round p.round + 1.  An engine without a downtime or a netsplit
+// passes null pointers and runs the first two tests only.
+__device__ __forceinline__ bool send_lost(const DevGraph& gs, const RoundParams& p, const Downtime& d,
+                                          const Netsplit& ns, int64_t v, int32_t u, int64_t slot) {
   if (gs.gone && gs.gone[slot]) return true;
   if (p.churn_thr &&
       churn_dropped((uint32_t)p.round, gidx(gs, v), gidx(gs, u), p.churn_thr, p.cseed_lo, p.cseed_hi))
     return true;
-  return d.from && downtime::offline(p.round + 1, d.from[u], d.until[u]);
+  if (d.from && downtime::offline(p.round + 1, d.from[u], d.until[u])) return true;
+  return link_cut(ns, p.round + 1, v, u);
 }
 
 // Anti-entropy: the connection peer v (deg >= 1) sent its request of round `rr` to (philox.h).

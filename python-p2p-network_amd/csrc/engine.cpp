@@ -48,6 +48,7 @@
 #include "../../include/p2pgpu.h"
 #include "anti_entropy.h"
 #include "downtime.h"
+#include "netsplit.h"
 #include "internal.h"
 #include "latency.h"
 #include "philox.h"
@@ -277,6 +278,10 @@ struct p2pg_engine {
   int32_t* d_down_until = nullptr;
   bool down_on = false;
   downtime::Sweep down_sweep;
+  // Network partition (p2pg_set_netsplit): peer v is on side d_side[v] (uploaded once by the call);
+  // the connections between sides are cut in the rounds of ns_win (empty: no netsplit).
+  int32_t* d_side = nullptr;
+  netsplit::Window ns_win;
   // Anti-entropy (p2pg_set_anti_entropy; anti_entropy.h, relay_pull.hip): the request rounds and
   // the partner draw's key.  The reply plane, its bitmap and the exchange's counter shards exist
   // only while it is set (with a state: they are sized by W).  pull_round = the arrival round the
@@ -459,6 +464,8 @@ void free_graph(p2pg_engine* e) {
   e->h_down_until.clear();
   e->down_sweep.build(0, nullptr, nullptr);
   e->down_on = false;
+  dfree(e->d_side);
+  e->ns_win = netsplit::Window{};
   free_pull(e);
   e->ae = anti_entropy::Setting{};
   e->ae_seed = 0;
@@ -670,16 +677,19 @@ int check_scatter_list(p2pg_engine* e, unsigned long long listed) {
 // Arrivals (p2pg_round_stats.received): a churn or downtime run with P2PG_FLAG_RECEIVED counts the
 // lost sends of every round.
 bool count_lost_on(const p2pg_engine* e) {
-  return (e->cfg.churn_threshold != 0 || e->down_on) && (e->cfg.flags & P2PG_FLAG_RECEIVED);
+  return (e->cfg.churn_threshold != 0 || e->down_on || e->ns_win.on()) && (e->cfg.flags & P2PG_FLAG_RECEIVED);
 }
 // Is the `received` counter of round r exact?  No churn, or the losses counted; with a downtime
-// whose losses are not counted, every round outside min(from) <= r < max(until).
+// whose losses are not counted, every round outside min(from) <= r < max(until); with a netsplit
+// whose losses are not counted, every round that is no cut round.
 bool received_exact(const p2pg_engine* e, int32_t r) {
   if (count_lost_on(e)) return true;
-  return e->cfg.churn_threshold == 0 && !(e->down_on && e->down_sweep.in_span(r));
+  return e->cfg.churn_threshold == 0 && !(e->down_on && e->down_sweep.in_span(r)) && !e->ns_win.cut_round(r);
 }
 // The device's view of the downtime (null pointers without one: send_lost, device_util.h).
 Downtime down(const p2pg_engine* e) { return Downtime{e->d_down_from, e->d_down_until}; }
+// The device's view of the netsplit (a null side without one).
+Netsplit cut(const p2pg_engine* e) { return Netsplit{e->d_side, e->ns_win.from, e->ns_win.until}; }
 // The device's view of the anti-entropy exchange whose replies arrived in round r: the reply plane
 // while it still belongs to that round (until the next gather), else null pointers -- find_parent
 // and the sender walks of k_sends / k_peer_tally then do what they do without the setting.
@@ -768,9 +778,9 @@ hipError_t flush_peer_tally(p2pg_engine* e, const DevGraph& gs) {
   p.round = r;
   hipError_t x = hipSuccess;
   if (tally_on(e))
-    x = launch_peer_tally(gs, graph_for_arrivals(e, r), e->st, p, down(e), pull_of(e, r), e->d_tsent, e->d_trecv, e->stream);
+    x = launch_peer_tally(gs, graph_for_arrivals(e, r), e->st, p, down(e), cut(e), pull_of(e, r), e->d_tsent, e->d_trecv, e->stream);
   if (x == hipSuccess && cost_on(e))
-    x = launch_msg_cost(gs, graph_for_arrivals(e, r), e->st, p, down(e), pull_of(e, r), e->d_cscratch, e->d_csent,
+    x = launch_msg_cost(gs, graph_for_arrivals(e, r), e->st, p, down(e), cut(e), pull_of(e, r), e->d_cscratch, e->d_csent,
                         e->d_crecv, e->stream);
   return x;
 }
@@ -783,7 +793,7 @@ hipError_t enqueue_lost_count(p2pg_engine* e, const DevGraph& gs, const DevGraph
   RoundParams p = params(e);
   p.round = r;
   if (x == hipSuccess)
-    x = launch_sends(gs, gp, e->st, p, down(e), pull_of(e, r), false, 0, nullptr, nullptr, nullptr, nullptr, e->d_cnt2, e->stream);
+    x = launch_sends(gs, gp, e->st, p, down(e), cut(e), pull_of(e, r), false, 0, nullptr, nullptr, nullptr, nullptr, e->d_cnt2, e->stream);
   if (x == hipSuccess)
     x = hipMemcpyAsync(e->h_cnt2, e->d_cnt2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream);
   return x;
@@ -1503,6 +1513,9 @@ int p2pg_set_ttl(p2pg_engine* e, int32_t M, const int32_t* ttl) {
   if (finite && e->ae.on())
     return fail(e, P2PG_ERR_STATE, "set_ttl: hop limits are not available together with anti-entropy "
                                    "(p2pg_set_anti_entropy): a pulled message's remaining budget is no function of the round");
+  if (finite && e->ns_win.on())
+    return fail(e, P2PG_ERR_STATE, "set_ttl: hop limits are not available together with a netsplit "
+                                   "(p2pg_set_netsplit): their held-back pushes would need the cut as well");
   if (!finite && e->h_ttl.empty()) return P2PG_OK;  // nothing set, nothing to remove
   if (finite)
     e->h_ttl.assign(ttl, ttl + M);
@@ -1527,6 +1540,9 @@ int p2pg_set_relay_policy(p2pg_engine* e, int64_t V, const uint32_t* thr, uint64
   if (any && e->ae.on())
     return fail(e, P2PG_ERR_STATE, "set_relay_policy: a relay policy is not available together with anti-entropy "
                                    "(p2pg_set_anti_entropy)");
+  if (any && e->ns_win.on())
+    return fail(e, P2PG_ERR_STATE, "set_relay_policy: a relay policy is not available together with a netsplit "
+                                   "(p2pg_set_netsplit): its held-back pushes would need the cut as well");
   if (!any && !e->pol_on) return P2PG_OK;  // nothing set, nothing to remove
   HIPCHK(e, hipSetDevice(e->cfg.device));
   HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -1617,6 +1633,57 @@ int p2pg_set_downtime(p2pg_engine* e, int64_t V, const int32_t* from, const int3
 
 int p2pg_peer_offline(int32_t round, int32_t from, int32_t until) {
   return downtime::offline(round, from, until) ? 1 : 0;
+}
+
+int p2pg_set_netsplit(p2pg_engine* e, int64_t V, const int32_t* side, int32_t cut_from, int32_t cut_until) {
+  if (!e) return fail(e, P2PG_ERR_ARG, "set_netsplit: no engine");
+  if (!e->d_rowptr) return fail(e, P2PG_ERR_STATE, "set_netsplit: load a graph first");
+  if (V != e->V) return fail(e, P2PG_ERR_ARG, "set_netsplit: V differs from the engine's peer count");
+  if (side) {  // (side = NULL removes the setting whatever the window)
+    const netsplit::Bad w = netsplit::check_window(cut_from, cut_until);
+    if (w != netsplit::OK)
+      return fail(e, P2PG_ERR_ARG, w == netsplit::BAD_FROM ? "set_netsplit: cut_from below 0" : "set_netsplit: cut_until below 0");
+    const int64_t v = netsplit::first_bad_side(V, side);
+    if (v >= 0) return fail(e, P2PG_ERR_ARG, "set_netsplit: peer " + std::to_string(v) + ": a negative side");
+  }
+  if (partitioned(e))
+    return fail(e, P2PG_ERR_STATE, "set_netsplit: a netsplit is not available on a vertex-partitioned rank");
+  if (e->begun) return fail(e, P2PG_ERR_STATE, "set_netsplit: a round has begun (step_begin)");
+  if (e->have_state && e->round > 0)
+    return fail(e, P2PG_ERR_STATE, "set_netsplit: a round has run (set the netsplit before round 0, or after p2pg_reset)");
+  if (!e->failed.empty()) return fail(e, P2PG_ERR_STATE, "set_netsplit: " + e->failed);
+  const bool any = netsplit::any(V, e->h_rowptr.data(), e->h_colidx.data(), side, cut_from, cut_until);
+  if (any && !e->h_ttl.empty())
+    return fail(e, P2PG_ERR_STATE, "set_netsplit: not available together with hop limits (p2pg_set_ttl)");
+  if (any && e->pol_on)
+    return fail(e, P2PG_ERR_STATE, "set_netsplit: not available together with a relay policy (p2pg_set_relay_policy)");
+  if (any && e->arr_round >= 0)
+    return fail(e, P2PG_ERR_STATE, "set_netsplit: not available after a topology update (p2pg_update_edges)");
+  if (!any && !e->ns_win.on()) return P2PG_OK;  // nothing set, nothing to remove
+  HIPCHK(e, hipSetDevice(e->cfg.device));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (any) {
+    int32_t* ds = nullptr;
+    const size_t nb = sizeof(int32_t) * (size_t)V;
+    hipError_t x = hipMalloc((void**)&ds, nb);
+    if (x == hipSuccess) x = hipMemcpy(ds, side, nb, hipMemcpyHostToDevice);
+    if (x != hipSuccess) {
+      if (ds) (void)hipFree(ds);
+      return fail(e, P2PG_ERR_HIP, std::string("set_netsplit: ") + hipGetErrorString(x));
+    }
+    dfree(e->d_side);
+    e->d_side = ds;
+    e->ns_win.from = cut_from;
+    e->ns_win.until = cut_until;
+  } else {  // no sides, an empty window or no crossing connection: the engine without this call
+    dfree(e->d_side);
+    e->ns_win = netsplit::Window{};
+  }
+  return P2PG_OK;
+}
+
+int p2pg_link_cut(int32_t round, int32_t side_a, int32_t side_b, int32_t cut_from, int32_t cut_until) {
+  return netsplit::link_cut(round, side_a, side_b, cut_from, cut_until) ? 1 : 0;
 }
 
 int p2pg_set_anti_entropy(p2pg_engine* e, int32_t first, int32_t last, int32_t period, uint64_t seed) {
@@ -1960,6 +2027,9 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   // Anti-entropy: the replies of request round e->round - 2 arrive in this round.
   const bool pull = e->ae.on() && e->ae.arrival_round(e->round);
   facts.pull = pull;
+  // Netsplit: the cut acts on this round -- a flood round receives over cut connections (a cut
+  // round > 0), a gossip round's sends arrive in a cut round.
+  facts.cut = gossip ? e->ns_win.cut_sends(e->round) : e->round > 0 && e->ns_win.cut_round(e->round);
   facts.skip_frontier = e->skip_frontier;
   const rp::RoundPlan plan = rp::plan_round(e->hist, e->rules, caps, facts);
   p.store_f = plan.store_f;
@@ -1969,7 +2039,7 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
     if ((rc = ensure_pull(e))) return rc;
     HIPCHK(e, hipMemsetAsync(e->d_pull_cnt, 0, PULL_BYTES, e->stream));
     e->pull_round = e->round;
-    if ((rc = timed(e, 0, [&] { return launch_pull_gather(g, s, p, down(e), pull_of(e, e->round), e->stream); })))
+    if ((rc = timed(e, 0, [&] { return launch_pull_gather(g, s, p, down(e), cut(e), pull_of(e, e->round), e->stream); })))
       return rc;
   }
   uint64_t tot[STAT_N] = {0};
@@ -1999,6 +2069,9 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
       break;
     case rp::Receive::FloodPull:
       if ((rc = timed(e, 1, [&] { return launch_flood_pull(g, s, p, e->hp, e->stream); }))) return rc;
+      break;
+    case rp::Receive::FloodPullCut:  // the copies over cut connections do not arrive (relay_netsplit.hip)
+      if ((rc = timed(e, 1, [&] { return launch_pull_cut(g, s, p, cut(e), e->hp, e->stream); }))) return rc;
       break;
     case rp::Receive::GossipPull:  // (a partitioned rank gets here only if part_dense)
       if ((rc = timed(e, 5, [&] {
@@ -2030,7 +2103,7 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
       return rc;
   if (s.hop)
     if ((rc = timed(e, 3, [&] {
-           return launch_record(graph_for_arrivals(e, e->round), s, p, pull_of(e, e->round), e->stream);
+           return launch_record(graph_for_arrivals(e, e->round), s, p, pull_of(e, e->round), cut(e), e->stream);
          })))
       return rc;
   auto read_stats = [&]() -> int {
@@ -2047,7 +2120,11 @@ int p2pg_step(p2pg_engine* e, p2pg_round_stats* out) {
   };
   // did this round's pushes go to E?  The fused and update+push launches pushed every source
   bool pushed_e = plan.push == rp::Push::Made;
-  if (gossip && !pushed_e && !plan.held) {
+  if (gossip && plan.push == rp::Push::AtomicCut) {
+    // the sends arrive in a cut round: row atomics, the picks over cut connections left out
+    p.dedup_push = rp::push_dedup(e->hist, e->rules);
+    if ((rc = timed(e, 2, [&] { return launch_push_cut(g, s, p, cut(e), e->stream); }))) return rc;
+  } else if (gossip && !pushed_e && !plan.held) {
     // the push the plan names, after the round's own counters where it asks for them
     if (plan.mid_read && (rc = read_stats())) return rc;
     const bool use_e =
@@ -2199,6 +2276,7 @@ static bool decay_batchable(const p2pg_engine* e) {
   f.expiry_ahead = expiry_ahead(e, e->round);
   f.offline_ahead = e->down_on && e->down_sweep.offline_ahead(e->round);
   f.pull_ahead = e->ae.arrival_ahead(e->round);
+  f.cut_ahead = e->ns_win.cut_ahead(e->round);
   f.frontier_needed = frontier_needed(e);
   f.autostop = !(e->cfg.flags & P2PG_FLAG_NO_AUTOSTOP);
   f.auto_buf = e->auto_buf != nullptr;
@@ -2233,7 +2311,7 @@ static int run_decay_batch(p2pg_engine* e, int32_t R, p2pg_round_stats* out, int
     if (i + 2 < n_left && partial_rows(e)) p.store_f = 2;
     partial[i] = p.store_f == 2;
     rc = timed(e, 4, [&] { return launch_gossip_update(g, s, p, e->stream); });
-    if (rc == P2PG_OK && s.hop) rc = timed(e, 3, [&] { return launch_record(g, s, p, pull_of(e, -1), e->stream); });
+    if (rc == P2PG_OK && s.hop) rc = timed(e, 3, [&] { return launch_record(g, s, p, pull_of(e, -1), cut(e), e->stream); });
     p.dedup_push = rp::push_dedup(e->hist, e->rules);
     if (rc == P2PG_OK)
       rc = timed(e, 2, [&] {
@@ -2339,7 +2417,7 @@ int p2pg_get_new_deliveries(p2pg_engine* e, int64_t cap, int32_t* peer, int32_t*
   HIPCHK(e, hipMalloc((void**)&dpar, sizeof(int32_t) * c));
   HIPCHK(e, hipMalloc((void**)&dcnt, sizeof(unsigned long long)));
   HIPCHK(e, hipMemsetAsync(dcnt, 0, sizeof(unsigned long long), e->stream));
-  hipError_t lr = launch_deliveries(g, e->st, p, pull_of(e, p.round), cap, dpeer, dmsg, dpar, dcnt, e->stream);
+  hipError_t lr = launch_deliveries(g, e->st, p, pull_of(e, p.round), cut(e), cap, dpeer, dmsg, dpar, dcnt, e->stream);
   unsigned long long cnt = 0;
   if (lr == hipSuccess) lr = hipMemcpyAsync(&cnt, dcnt, sizeof(cnt), hipMemcpyDeviceToHost, e->stream);
   if (lr == hipSuccess) lr = hipStreamSynchronize(e->stream);
@@ -2418,7 +2496,7 @@ int p2pg_get_sends(p2pg_engine* e, int64_t cap, int32_t* sender, int32_t* receiv
   if (lr == hipSuccess) lr = hipMalloc((void**)&dl, c);
   if (lr == hipSuccess) lr = hipMemsetAsync(e->d_cnt2, 0, 2 * sizeof(unsigned long long), e->stream);
   if (lr == hipSuccess)
-    lr = launch_sends(graph(e), graph_for_arrivals(e, r), e->st, p, down(e), pull_of(e, r), true, cap, ds, dr, dm, dl, e->d_cnt2, e->stream);
+    lr = launch_sends(graph(e), graph_for_arrivals(e, r), e->st, p, down(e), cut(e), pull_of(e, r), true, cap, ds, dr, dm, dl, e->d_cnt2, e->stream);
   unsigned long long cnt = 0;
   if (lr == hipSuccess) lr = hipMemcpyAsync(&cnt, e->d_cnt2, sizeof(cnt), hipMemcpyDeviceToHost, e->stream);
   if (lr == hipSuccess) lr = hipStreamSynchronize(e->stream);
@@ -2460,6 +2538,8 @@ int p2pg_drop_relays(p2pg_engine* e, int64_t n, const int32_t* peer, const int32
   if (!e || n < 0 || (n > 0 && (!peer || !msg))) return fail(e, P2PG_ERR_ARG, "drop_relays: bad arguments");
   if (e && e->ae.on())
     return fail(e, P2PG_ERR_STATE, "drop_relays: not available while anti-entropy is set (p2pg_set_anti_entropy)");
+  if (e && e->ns_win.on())
+    return fail(e, P2PG_ERR_STATE, "drop_relays: not available while a netsplit is set (p2pg_set_netsplit)");
   int rc = sends_state(e, "drop_relays");
   if (rc) return rc;
   if (deferred_on(e) && e->tally_read_at == e->round)
@@ -2764,6 +2844,9 @@ int p2pg_set_global_ids(p2pg_engine* e, const int32_t* gid) {
   if (gid && e->pol_on)
     return fail(e, P2PG_ERR_STATE, "set_global_ids: a relay policy (p2pg_set_relay_policy) is not available on a "
                                    "vertex-partitioned rank");
+  if (gid && e->ns_win.on())
+    return fail(e, P2PG_ERR_STATE, "set_global_ids: a netsplit (p2pg_set_netsplit) is not available on a "
+                                   "vertex-partitioned rank");
   if (gid && e->down_on)
     return fail(e, P2PG_ERR_STATE, "set_global_ids: peer downtime (p2pg_set_downtime) is not available on a "
                                    "vertex-partitioned rank");
@@ -2981,6 +3064,8 @@ int p2pg_update_edges(p2pg_engine* e, int64_t n_add, const int32_t* add, int64_t
     return fail(e, P2PG_ERR_STATE, "update_edges: not supported on a vertex-partitioned rank");
   if (e->ae.on())
     return fail(e, P2PG_ERR_STATE, "update_edges: not available while anti-entropy is set (p2pg_set_anti_entropy)");
+  if (e->ns_win.on())
+    return fail(e, P2PG_ERR_STATE, "update_edges: not available while a netsplit is set (p2pg_set_netsplit)");
   if (e->arr_round >= 0 && e->arr_round == e->round)
     return fail(e, P2PG_ERR_STATE, "update_edges: one update per round boundary");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "update_edges: a round has begun (step_begin)");
@@ -3244,6 +3329,8 @@ int p2pg_snapshot(p2pg_engine* e, void* buf, int64_t cap) {
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold a relay policy (p2pg_set_relay_policy)");
   if (e->down_on)
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold peer downtime (p2pg_set_downtime)");
+  if (e->ns_win.on())
+    return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold a netsplit (p2pg_set_netsplit)");
   if (e->ae.on())
     return fail(e, P2PG_ERR_STATE, "snapshot: snapshots do not hold anti-entropy exchanges (p2pg_set_anti_entropy)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "snapshot: a round has begun (step_begin)");
@@ -3322,6 +3409,8 @@ int p2pg_restore(p2pg_engine* e, const void* buf, int64_t size) {
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold a relay policy (p2pg_set_relay_policy)");
   if (e->down_on)
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold peer downtime (p2pg_set_downtime)");
+  if (e->ns_win.on())
+    return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold a netsplit (p2pg_set_netsplit)");
   if (e->ae.on())
     return fail(e, P2PG_ERR_STATE, "restore: snapshots do not hold anti-entropy exchanges (p2pg_set_anti_entropy)");
   if (e->begun) return fail(e, P2PG_ERR_STATE, "restore: a round has begun (step_begin)");

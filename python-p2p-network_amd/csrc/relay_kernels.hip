@@ -2282,8 +2282,9 @@ __global__ __launch_bounds__(256, FUSED_WAVES) void k_gossip_fused(DevGraph g, D
 // In an arrival round of an anti-entropy exchange (pl.R set) the reply is one more arriving packet:
 // if it carried m, u's partner of request round p.round - 2 is a sender too, and the result is the
 // lower of the two ids.
+// A copy over a connection that is cut in round p.round (ns, p2pg_set_netsplit) did not arrive.
 __device__ int32_t find_parent(const DevGraph& g, const DevState& st, const RoundParams& p, const Pull& pl,
-                               int64_t u, int m) {
+                               const Netsplit& ns, int64_t u, int m) {
   const int prv = (p.round & 1) ^ 1;
   const int W = st.W;
   const uint64_t bit = 1ull << (m & 63);
@@ -2299,6 +2300,7 @@ __device__ int32_t find_parent(const DevGraph& g, const DevState& st, const Roun
     if (p.churn_thr && churn_dropped((uint32_t)(p.round - 1), gidx(g, u), gidx(g, v),
                                      p.churn_thr, p.cseed_lo, p.cseed_hi))
       continue;
+    if (link_cut(ns, p.round, u, v)) continue;
     if (p.mode == 1) {
       const int64_t vb = g.rowptr[v];
       // a ghost sender (partitioned runs): its global degree and u's place in its global row
@@ -2327,7 +2329,8 @@ __device__ int32_t find_parent(const DevGraph& g, const DevState& st, const Roun
   return pp >= 0 ? pp : -2;
 }
 
-__global__ __launch_bounds__(256) void k_record(DevGraph g, DevState st, RoundParams p, Pull pl) {
+__global__ __launch_bounds__(256) void k_record(DevGraph g, DevState st, RoundParams p, Pull pl,
+                                                Netsplit ns) {
   const int lane = threadIdx.x & 63;
   const int wib = wave_in_block();
   const int cur = p.round & 1;
@@ -2349,7 +2352,7 @@ __global__ __launch_bounds__(256) void k_record(DevGraph g, DevState st, RoundPa
           f &= f - 1ull;
           const int m = w * 64 + bit;
           st.hop[u * st.M + m] = p.round;
-          const int32_t par = p.round == 0 ? -1 : find_parent(g, st, p, pl, u, m);
+          const int32_t par = p.round == 0 ? -1 : find_parent(g, st, p, pl, ns, u, m);
           st.parent[u * st.M + m] = par < 0 ? -1 : par;  // (no sender: an origination)
         }
       }
@@ -2358,7 +2361,7 @@ __global__ __launch_bounds__(256) void k_record(DevGraph g, DevState st, RoundPa
 }
 
 __global__ __launch_bounds__(256) void k_deliveries(DevGraph g, DevState st, RoundParams p, Pull pl,
-                                                    int64_t cap, int32_t* peer, int32_t* msg,
+                                                    Netsplit ns, int64_t cap, int32_t* peer, int32_t* msg,
                                                     int32_t* parent,
                                                     unsigned long long* counter) {
   const int lane = threadIdx.x & 63;
@@ -2385,7 +2388,7 @@ __global__ __launch_bounds__(256) void k_deliveries(DevGraph g, DevState st, Rou
           if ((int64_t)pos < cap) {
             peer[pos] = (int32_t)u;
             msg[pos] = m;
-            const int32_t par = p.round == 0 ? -1 : find_parent(g, st, p, pl, u, m);
+            const int32_t par = p.round == 0 ? -1 : find_parent(g, st, p, pl, ns, u, m);
             parent[pos] = par < 0 ? -1 : par;  // (no sender: an origination)
           }
         }
@@ -2871,17 +2874,17 @@ hipError_t launch_clear_arrivals(const DevState& st, int32_t round, int64_t V, h
 }
 
 hipError_t launch_record(const DevGraph& g, const DevState& st, const RoundParams& p, const Pull& pl,
-                         hipStream_t s) {
+                         const Netsplit& ns, hipStream_t s) {
   const int grid = grid_tasks((g.V + 31) >> 5);
-  hipLaunchKernelGGL(k_record, dim3(grid), dim3(256), 0, s, g, st, p, pl);
+  hipLaunchKernelGGL(k_record, dim3(grid), dim3(256), 0, s, g, st, p, pl, ns);
   return hipGetLastError();
 }
 
 hipError_t launch_deliveries(const DevGraph& g, const DevState& st, const RoundParams& p, const Pull& pl,
-                             int64_t cap, int32_t* peer, int32_t* msg, int32_t* parent,
+                             const Netsplit& ns, int64_t cap, int32_t* peer, int32_t* msg, int32_t* parent,
                              unsigned long long* counter, hipStream_t s) {
   const int grid = grid_tasks((g.V + 31) >> 5);
-  hipLaunchKernelGGL(k_deliveries, dim3(grid), dim3(256), 0, s, g, st, p, pl, cap, peer, msg,
+  hipLaunchKernelGGL(k_deliveries, dim3(grid), dim3(256), 0, s, g, st, p, pl, ns, cap, peer, msg,
                      parent, counter);
   return hipGetLastError();
 }

@@ -3,8 +3,8 @@
 // connection p (pull_partner_slot, philox.h).  p answers in round r + 1, after that round's
 // arrivals and originations, with every message it has seen and the digest lacks; the reply
 // arrives in round r + 2 as one more packet from sender p.  Request and reply are sends of their
-// rounds: lost by the churn draw of (round, {u, p}) or because their receiver is offline in the
-// round they would arrive in.  Nothing but the arrivals is state, so request and reply rounds
+// rounds: lost by the churn draw of (round, {u, p}), because their receiver is offline in the round
+// they would arrive in, or because the connection is cut in that round (p2pg_set_netsplit).  Nothing but the arrivals is state, so request and reply rounds
 // launch nothing; both kernels here run in the arrival round a = r + 2, around the receive pass
 // the plan chose (flood pull, gossip update or gossip pull):
 //
@@ -43,7 +43,7 @@ __device__ __forceinline__ void flush_pull(unsigned long long* cnt, int idx, uin
 // A peer whose row is full (S bit) or whose exchange failed writes nothing but its counts; its R
 // row is stale and its PB bit clear.  No LDS, no global atomics but the counter shards.
 template <bool NARROW>
-__global__ __launch_bounds__(256) void k_pull_gather(DevGraph g, DevState st, RoundParams p, Downtime d, Pull pl) {
+__global__ __launch_bounds__(256) void k_pull_gather(DevGraph g, DevState st, RoundParams p, Downtime d, Netsplit ns, Pull pl) {
   const int lane = threadIdx.x & 63;
   const int W = st.W;
   const int32_t rq = p.round - 2;  // the request round
@@ -75,11 +75,11 @@ __global__ __launch_bounds__(256) void k_pull_gather(DevGraph g, DevState st, Ro
         // the request is a send of round rq to pp, the reply a send of round rq + 1 to v
         const bool req_lost =
             churn_dropped((uint32_t)rq, gidx(g, v), gidx(g, pp), p.churn_thr, p.cseed_lo, p.cseed_hi) ||
-            (d.from && downtime::offline(rq + 1, d.from[pp], d.until[pp]));
+            (d.from && downtime::offline(rq + 1, d.from[pp], d.until[pp])) || link_cut(ns, rq + 1, v, pp);
         const bool rep_lost =
             !req_lost &&
             (churn_dropped((uint32_t)(rq + 1), gidx(g, pp), gidx(g, v), p.churn_thr, p.cseed_lo, p.cseed_hi) ||
-             (d.from && downtime::offline(rq + 2, d.from[v], d.until[v])));
+             (d.from && downtime::offline(rq + 2, d.from[v], d.until[v])) || link_cut(ns, rq + 2, pp, v));
         c_req += 1;
         c_reql += req_lost ? 1 : 0;
         c_rep += req_lost ? 0 : 1;  // (sent even if it lists nothing)
@@ -208,12 +208,12 @@ __global__ __launch_bounds__(256) void k_pull_apply(DevGraph g, DevState st, Rou
 }  // namespace
 
 hipError_t launch_pull_gather(const DevGraph& g, const DevState& st, const RoundParams& p, const Downtime& d,
-                              const Pull& pl, hipStream_t s) {
+                              const Netsplit& ns, const Pull& pl, hipStream_t s) {
   const dim3 grid(grid_tasks((g.V + 31) >> 5));
   if (st.W <= 32)
-    hipLaunchKernelGGL(k_pull_gather<true>, grid, dim3(256), 0, s, g, st, p, d, pl);
+    hipLaunchKernelGGL(k_pull_gather<true>, grid, dim3(256), 0, s, g, st, p, d, ns, pl);
   else
-    hipLaunchKernelGGL(k_pull_gather<false>, grid, dim3(256), 0, s, g, st, p, d, pl);
+    hipLaunchKernelGGL(k_pull_gather<false>, grid, dim3(256), 0, s, g, st, p, d, ns, pl);
   return hipGetLastError();
 }
 

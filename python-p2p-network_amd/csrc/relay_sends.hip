@@ -16,12 +16,14 @@ namespace {
 
 // Did neighbour y's round-(r-1) send of this lane's word reach v?  (find_parent's test, word-wide:
 // y relayed in round r-1 -- its A bit and frontier word --, the connection was not removed
-// before the messages arrived, and churn did not drop it.)  Flood only; wave-uniform y.
+// before the messages arrived, churn did not drop it, and the connection is not cut in round r.)
+// Flood only; wave-uniform y.
 __device__ __forceinline__ uint64_t relay_sends(const DevGraph& gp, const DevState& st, const RoundParams& p,
-                                                int64_t v, int32_t y, int64_t slot, int w) {
+                                                const Netsplit& ns, int64_t v, int32_t y, int64_t slot, int w) {
   const int prv = (p.round & 1) ^ 1;
   if (gp.gone && gp.gone[slot]) return 0ull;
   if (!bit_test(st.A[prv], y)) return 0ull;
+  if (link_cut(ns, p.round, v, y)) return 0ull;
   if (p.churn_thr && churn_dropped((uint32_t)(p.round - 1), gidx(gp, v), gidx(gp, y), p.churn_thr,
                                    p.cseed_lo, p.cseed_hi))
     return 0ull;
@@ -31,9 +33,9 @@ __device__ __forceinline__ uint64_t relay_sends(const DevGraph& gp, const DevSta
 // ... or, anti-entropy, did y's reply carry it?  partner = v's partner of the exchange whose
 // replies arrive in this round (-1: none arrived at v), pw = what the reply carried in this word.
 __device__ __forceinline__ uint64_t prev_sends(const DevGraph& gp, const DevState& st, const RoundParams& p,
-                                               int64_t v, int32_t y, int64_t slot, int w, int32_t partner,
+                                               const Netsplit& ns, int64_t v, int32_t y, int64_t slot, int w, int32_t partner,
                                                uint64_t pw) {
-  return relay_sends(gp, st, p, v, y, slot, w) | (y == partner ? pw : 0ull);
+  return relay_sends(gp, st, p, ns, v, y, slot, w) | (y == partner ? pw : 0ull);
 }
 
 // One wave per active peer v of round r = p.round (A[r&1]), lane = word of a 64-word slice.
@@ -42,13 +44,13 @@ __device__ __forceinline__ uint64_t prev_sends(const DevGraph& gp, const DevStat
 // node.py:106-112; none at the origin, r = 0).  Walking v's gp row ascending, `rem` holds the
 // bits whose sender is not found yet; a neighbour y takes rem & (y's sends) as its own.
 // Gossip: one send per Philox pick (the sender is not excluded).
-// A send is lost by send_lost (device_util.h): a removed connection, churn, or a receiver that is
-// offline in round r + 1.
+// A send is lost by send_lost (device_util.h): a removed connection, churn, a receiver that is
+// offline in round r + 1, or a connection that is cut in round r + 1.
 // EMIT: records at atomic positions (< cap); else only the lost sends are counted (cnt[1]) and
 // peers without a lost connection are skipped.  cnt[0] = sends emitted.
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_sends(DevGraph gs, DevGraph gp, DevState st, RoundParams p,
-                                               Downtime d, Pull pl, int64_t cap, int32_t* __restrict__ snd,
+                                               Downtime d, Netsplit ns, Pull pl, int64_t cap, int32_t* __restrict__ snd,
                                                int32_t* __restrict__ rcv, int32_t* __restrict__ msg,
                                                uint8_t* __restrict__ lostf,
                                                unsigned long long* __restrict__ cnt) {
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(256) void k_sends(DevGraph gs, DevGraph gp, DevStat
         last_lost = -1;
         for (int64_t j0 = beg; j0 < end; j0 += 64) {
           const int64_t j = j0 + lane;
-          const bool l = j < end && send_lost(gs, p, d, v, gs.colidx[j], j);
+          const bool l = j < end && send_lost(gs, p, d, ns, v, gs.colidx[j], j);
           const uint64_t bl = __ballot(l);
           if (bl) last_lost = j0 + 63 - __builtin_clzll(bl);
         }
@@ -107,14 +109,14 @@ __global__ __launch_bounds__(256) void k_sends(DevGraph gs, DevGraph gp, DevStat
             while (jp < ep) {
               const int32_t y = gp.colidx[jp];
               if (y > u) break;
-              const uint64_t sy = __ballot(rem != 0ull) ? prev_sends(gp, st, p, v, y, jp, w, partner, pw) : 0ull;
+              const uint64_t sy = __ballot(rem != 0ull) ? prev_sends(gp, st, p, ns, v, y, jp, w, partner, pw) : 0ull;
               if (y == u) pu = rem & sy;
               rem &= ~sy;
               ++jp;
               if (y == u) break;
             }
             const uint64_t out = f & ~pu;
-            const bool l = send_lost(gs, p, d, v, u, j);
+            const bool l = send_lost(gs, p, d, ns, v, u, j);
             if (EMIT) {
               uint64_t o = out;
               while (o) {
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(256) void k_sends(DevGraph gs, DevGraph gp, DevStat
             for (int q = 0; q < k; ++q) {
               const int64_t j = beg + ((int)deg > p.fanout ? (int64_t)pk[q] : (int64_t)q);
               const int32_t u = gs.colidx[j];
-              const bool l = send_lost(gs, p, d, v, u, j);
+              const bool l = send_lost(gs, p, d, ns, v, u, j);
               put(v, u, m, l);
               n_lost += l ? 1u : 0u;
               n_sent += 1u;
@@ -204,13 +206,13 @@ __global__ __launch_bounds__(256) void k_rebuild_aw(DevState st, int32_t round, 
 }  // namespace
 
 hipError_t launch_sends(const DevGraph& gs, const DevGraph& gp, const DevState& st, const RoundParams& p,
-                        const Downtime& d, const Pull& pl, bool emit, int64_t cap, int32_t* snd, int32_t* rcv, int32_t* msg, uint8_t* lost,
+                        const Downtime& d, const Netsplit& ns, const Pull& pl, bool emit, int64_t cap, int32_t* snd, int32_t* rcv, int32_t* msg, uint8_t* lost,
                         unsigned long long* cnt, hipStream_t s) {
   const int grid = grid_tasks((gs.V + 31) >> 5);
   if (emit)
-    hipLaunchKernelGGL(k_sends<true>, dim3(grid), dim3(256), 0, s, gs, gp, st, p, d, pl, cap, snd, rcv, msg, lost, cnt);
+    hipLaunchKernelGGL(k_sends<true>, dim3(grid), dim3(256), 0, s, gs, gp, st, p, d, ns, pl, cap, snd, rcv, msg, lost, cnt);
   else
-    hipLaunchKernelGGL(k_sends<false>, dim3(grid), dim3(256), 0, s, gs, gp, st, p, d, pl, cap, snd, rcv, msg, lost, cnt);
+    hipLaunchKernelGGL(k_sends<false>, dim3(grid), dim3(256), 0, s, gs, gp, st, p, d, ns, pl, cap, snd, rcv, msg, lost, cnt);
   return hipGetLastError();
 }
 

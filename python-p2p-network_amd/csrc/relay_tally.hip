@@ -182,10 +182,11 @@ __global__ __launch_bounds__(256) void k_tally_fold(unsigned long long* __restri
 
 // k_sends' helpers (relay_sends.hip), same tests.
 __device__ __forceinline__ uint64_t prev_sends(const DevGraph& gp, const DevState& st, const RoundParams& p,
-                                               int64_t v, int32_t y, int64_t slot, int w) {
+                                               const Netsplit& ns, int64_t v, int32_t y, int64_t slot, int w) {
   const int prv = (p.round & 1) ^ 1;
   if (gp.gone && gp.gone[slot]) return 0ull;
   if (!bit_test(st.A[prv], y)) return 0ull;
+  if (link_cut(ns, p.round, v, y)) return 0ull;
   if (p.churn_thr && churn_dropped((uint32_t)(p.round - 1), gidx(gp, v), gidx(gp, y), p.churn_thr,
                                    p.cseed_lo, p.cseed_hi))
     return 0ull;
@@ -217,7 +218,7 @@ __device__ __forceinline__ int64_t find_slot(const DevGraph& gs, int64_t beg, in
 //   per connection in the wave's LDS table (rows of at most HUB_T connections), so the global
 //   atomics are one per connection that was picked; wider rows add per pick.
 __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, DevState st, RoundParams p,
-                                                    Downtime d, Pull pl,
+                                                    Downtime d, Netsplit ns, Pull pl,
                                                     unsigned long long* __restrict__ sent,
                                                     unsigned long long* __restrict__ received) {
   __shared__ uint32_t tab_all[WPB][HUB_T];
@@ -260,7 +261,7 @@ __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, De
             const int64_t j = j0 + lane;
             if (j < end) {
               const int32_t u = gs.colidx[j];
-              if (!send_lost(gs, p, d, v, u, j)) atomicAdd(received + u, (unsigned long long)n);
+              if (!send_lost(gs, p, d, ns, v, u, j)) atomicAdd(received + u, (unsigned long long)n);
             }
           }
           v_sent += (unsigned long long)n * deg;
@@ -271,7 +272,7 @@ __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, De
             const int64_t ep = gp.rowptr[v + 1];
             for (int64_t jp = gp.rowptr[v]; jp < ep && __ballot(rem != 0ull); ++jp) {
               const int32_t y = gp.colidx[jp];
-              const uint64_t sy = prev_sends(gp, st, p, v, y, jp, w) | (y == partner ? pw : 0ull);
+              const uint64_t sy = prev_sends(gp, st, p, ns, v, y, jp, w) | (y == partner ? pw : 0ull);
               const uint64_t pu = rem & sy;
               rem &= ~sy;
               if (!__ballot(pu != 0ull)) continue;
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, De
               const int64_t j = same ? jp : find_slot(gs, beg, end, y);
               if (j < 0) continue;  // no longer a connection: nothing was sent to it
               v_sent -= c;
-              if (lane == 0 && !send_lost(gs, p, d, v, y, j)) atomicAdd(received + y, 0ull - (unsigned long long)c);
+              if (lane == 0 && !send_lost(gs, p, d, ns, v, y, j)) atomicAdd(received + y, 0ull - (unsigned long long)c);
             }
           }
         } else {
@@ -300,7 +301,7 @@ __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, De
             } else {
               const int64_t j = beg + (int64_t)pick;
               const int32_t u = gs.colidx[j];
-              if (!send_lost(gs, p, d, v, u, j)) atomicAdd(received + u, 1ull);
+              if (!send_lost(gs, p, d, ns, v, u, j)) atomicAdd(received + u, 1ull);
             }
           };
           auto draw = [&](auto kc) {  // fanout <= 4: one Philox block per receipt, picks in registers
@@ -337,7 +338,7 @@ __global__ __launch_bounds__(256) void k_peer_tally(DevGraph gs, DevGraph gp, De
           if (c) {
             const int64_t j = beg + i;
             const int32_t u = gs.colidx[j];
-            if (!send_lost(gs, p, d, v, u, j)) atomicAdd(received + u, (unsigned long long)c);
+            if (!send_lost(gs, p, d, ns, v, u, j)) atomicAdd(received + u, (unsigned long long)c);
           }
         }
         wave_lds_sync();
@@ -427,7 +428,7 @@ __device__ __forceinline__ void wc_flush(WCount& k, uint32_t* lds, int lane) {
 // or, above drain_at >> COST_LDS_SHIFT (2^24 connections), one 64-bit atomic into the shard.
 // drain_at: COST_DRAIN (a launch argument so that a test can reach the drain and that last path).
 __global__ __launch_bounds__(256) void k_msg_cost(DevGraph gs, DevGraph gp, DevState st, RoundParams p,
-                                                  Downtime d, Pull pl, unsigned long long* __restrict__ scratch,
+                                                  Downtime d, Netsplit ns, Pull pl, unsigned long long* __restrict__ scratch,
                                                   int shards, uint32_t drain_at) {
   __shared__ uint32_t lds_s[64 * 64];
   __shared__ uint32_t lds_r[64 * 64];
@@ -445,7 +446,7 @@ __global__ __launch_bounds__(256) void k_msg_cost(DevGraph gs, DevGraph gp, DevS
   const int64_t nbt = (ntasks + WPB - 1) / WPB;
   const int64_t nitems = nbt * nsl;
   const bool same = gs.rowptr == gp.rowptr && gs.colidx == gp.colidx;
-  const bool lossless = !gs.gone && !p.churn_thr && !d.from;
+  const bool lossless = !gs.gone && !p.churn_thr && !d.from && !ns.side;
   const uint32_t lds_max = drain_at >> COST_LDS_SHIFT;
   unsigned long long* out_s = scratch + (size_t)(blockIdx.x & (shards - 1)) * (2 * nmsg);
   unsigned long long* out_r = out_s + nmsg;
@@ -545,7 +546,7 @@ __global__ __launch_bounds__(256) void k_msg_cost(DevGraph gs, DevGraph gp, DevS
       if (!lossless) {
         for (int64_t j0 = beg; j0 < end; j0 += 64) {
           const int64_t j = j0 + lane;
-          const uint64_t bal = __ballot(j < end && send_lost(gs, p, d, v, gs.colidx[j], j));
+          const uint64_t bal = __ballot(j < end && send_lost(gs, p, d, ns, v, gs.colidx[j], j));
           nlost += (uint32_t)__popcll(bal);
           if (use_map && lane < 2) lostmap[((j0 - beg) >> 5) + lane] = (uint32_t)(bal >> (32 * lane));
         }
@@ -561,14 +562,14 @@ __global__ __launch_bounds__(256) void k_msg_cost(DevGraph gs, DevGraph gp, DevS
           const int64_t ep = gp.rowptr[v + 1];
           for (int64_t jp = gp.rowptr[v]; jp < ep && __ballot(rem != 0ull); ++jp) {
             const int32_t y = gp.colidx[jp];
-            const uint64_t sy = prev_sends(gp, st, p, v, y, jp, w) | (y == partner ? pw : 0ull);
+            const uint64_t sy = prev_sends(gp, st, p, ns, v, y, jp, w) | (y == partner ? pw : 0ull);
             const uint64_t pu = rem & sy;
             rem &= ~sy;
             if (!__ballot(pu != 0ull)) continue;
             const int64_t j = same ? jp : find_slot(gs, beg, end, y);
             if (j < 0) continue;  // no longer a connection: nothing was sent to it
             ex_s |= pu;
-            if (!send_lost(gs, p, d, v, y, j)) ex_r |= pu;
+            if (!send_lost(gs, p, d, ns, v, y, j)) ex_r |= pu;
           }
         }
         make_room(sl, deg);
@@ -600,7 +601,7 @@ __global__ __launch_bounds__(256) void k_msg_cost(DevGraph gs, DevGraph gp, DevS
               c += 1u - ((lostmap[pk[q] >> 5] >> (pk[q] & 31u)) & 1u);
             } else {
               const int64_t j = beg + (int64_t)pk[q];
-              if (!send_lost(gs, p, d, v, gs.colidx[j], j)) ++c;
+              if (!send_lost(gs, p, d, ns, v, gs.colidx[j], j)) ++c;
             }
           }
           if (c) atomicAdd(&lds_r[cost_idx((int)(m >> 6), (int)(m & 63u))], c);
@@ -672,7 +673,7 @@ __global__ __launch_bounds__(256) void k_cost_fold(unsigned long long* __restric
 int64_t cost_scratch_words(int32_t W) { return (int64_t)TALLY_SHARDS * 2 * ((W + 63) / 64) * 4096; }
 
 hipError_t launch_msg_cost(const DevGraph& gs, const DevGraph& gp, const DevState& st, const RoundParams& p,
-                           const Downtime& d, const Pull& pl, unsigned long long* scratch,
+                           const Downtime& d, const Netsplit& ns, const Pull& pl, unsigned long long* scratch,
                            unsigned long long* sent, unsigned long long* received, hipStream_t s) {
   if (gs.V <= 0 || st.W <= 0) return hipSuccess;
   static const uint32_t drain_at = [] {  // P2PG_COST_DRAIN: the tests' way to the LDS drain
@@ -684,7 +685,7 @@ hipError_t launch_msg_cost(const DevGraph& gs, const DevGraph& gp, const DevStat
   const int nsl = (st.W + 63) / 64;
   const int64_t n = (int64_t)nsl * 4096;
   const int64_t nbt = (((gs.V + 31) >> 5) + WPB - 1) / WPB;
-  hipLaunchKernelGGL(k_msg_cost, dim3(grid_tasks(nbt * nsl * WPB)), dim3(256), 0, s, gs, gp, st, p, d, pl, scratch,
+  hipLaunchKernelGGL(k_msg_cost, dim3(grid_tasks(nbt * nsl * WPB)), dim3(256), 0, s, gs, gp, st, p, d, ns, pl, scratch,
                      TALLY_SHARDS, drain_at);
   hipError_t r = hipGetLastError();
   if (r != hipSuccess) return r;
@@ -735,9 +736,9 @@ hipError_t launch_column_count(const uint64_t* plane, const uint32_t* A, int64_t
 }
 
 hipError_t launch_peer_tally(const DevGraph& gs, const DevGraph& gp, const DevState& st, const RoundParams& p,
-                             const Downtime& d, const Pull& pl, unsigned long long* sent,
+                             const Downtime& d, const Netsplit& ns, const Pull& pl, unsigned long long* sent,
                              unsigned long long* received, hipStream_t s) {
-  hipLaunchKernelGGL(k_peer_tally, dim3(grid_tasks((gs.V + 31) >> 5)), dim3(256), 0, s, gs, gp, st, p, d, pl, sent,
+  hipLaunchKernelGGL(k_peer_tally, dim3(grid_tasks((gs.V + 31) >> 5)), dim3(256), 0, s, gs, gp, st, p, d, ns, pl, sent,
                      received);
   return hipGetLastError();
 }

@@ -86,13 +86,18 @@ struct RoundFacts {
   bool pull = false;           // the replies of an anti-entropy exchange arrive in it
                                // (p2pg_set_anti_entropy): what they carried joins its first receipts
                                // between the receive pass and the push
+  bool cut = false;            // a netsplit acts on it (p2pg_set_netsplit): a flood round > 0 inside
+                               // the window receives over cut connections; a gossip round's sends
+                               // arrive in a round of the window
   bool skip_frontier = false;  // nobody observes its frontier rows (inside p2pg_run)
 };
 
-enum class Receive { Seed, Consume, FloodPull, GossipPull, Fused, UpdatePush, Update };
+// FloodPullCut: the flood pull of a cut round (relay_netsplit.hip).
+enum class Receive { Seed, Consume, FloodPull, GossipPull, Fused, UpdatePush, Update, FloodPullCut };
 // Made: by the receive pass (Fused, UpdatePush).  ByCounters: edge stores or row atomics by the
 // density of the round's own frontier (resolve_push).
-enum class Push { None, Made, Edge, Atomic, ByCounters };
+// AtomicCut: row atomics by the push that leaves out the picks over cut connections.
+enum class Push { None, Made, Edge, Atomic, ByCounters, AtomicCut };
 // The (peer, word) list of a lane-parallel row-atomic push: sized by the last round's pushed masks
 // or by the round's own active words (Counters: they are read first).
 enum class PushList { None, PrevSw, Counters };
@@ -180,12 +185,16 @@ inline bool push_dedup(const RoundHistory& h, const RoundRules& r) {
 // before the push, which leaves in the round, in the form the density rule gives.  The arrival
 // round of an anti-entropy exchange is planned like an offline round: k_pull_apply (relay_pull.hip)
 // ORs the pulled receipts into the rows before the push, so whole rows, unfused, never blind, not
-// held; request and reply rounds launch nothing and are no special rounds.  The rounds around a
-// special round keep every form they have.
+// held; request and reply rounds launch nothing and are no special rounds.  A round a netsplit acts
+// on is special as well.  In a flood it is a cut round, whose receive pass is the cut pull.  In gossip
+// it is a round whose sends arrive in a cut round: the loss is decided where the send is made, so it
+// receives and pushes in separate passes (never Fused / UpdatePush, no edge stores), keeps whole
+// frontier rows and pushes by the cut push (row atomics) at once, without reading its counters: not
+// held, no list.  The rounds around a special round keep every form they have.
 inline RoundPlan plan_round(const RoundHistory& h, const RoundRules& r, const RoundCaps& c,
                             const RoundFacts& f) {
   RoundPlan p;
-  const bool special = f.origination || f.expiry || f.policy || f.offline || f.pull;
+  const bool special = f.origination || f.expiry || f.policy || f.offline || f.pull || f.cut;
   // the update / pull-only pass of this round (fused and update+push rounds set their own): a
   // frontier nobody observes is written by its nonzero words only
   if (c.gossip && !special && f.skip_frontier && c.partial_rows) p.store_f = 2;
@@ -197,7 +206,7 @@ inline RoundPlan plan_round(const RoundHistory& h, const RoundRules& r, const Ro
   } else if (f.consume_next) {
     p.receive = Receive::Consume;
   } else if (!c.gossip) {
-    p.receive = Receive::FloodPull;
+    p.receive = f.cut ? Receive::FloodPullCut : Receive::FloodPull;
   } else if (h.last_push_e) {
     // the previous round stored per-edge masks: gather them (pull, no atomics); if this round is
     // predicted dense as well, the same pass also pushes its receipts
@@ -221,6 +230,11 @@ inline RoundPlan plan_round(const RoundHistory& h, const RoundRules& r, const Ro
   // choice is clear already) and to size the sparse push's list (else bounded by the last round's
   // pushed masks).  Not on a vertex-partitioned rank: rows other ranks pushed arrive by the
   // exchange, so this rank's own pushed masks bound nothing.
+  if (f.cut) {
+    p.push = Push::AtomicCut;
+    p.held = false;
+    return p;
+  }
   const bool blind = f.round > 0 && r.push_mode != 2 && !c.partitioned && !special &&
                      clearly_sparse(h, r, f.round) && h.prev_sw > 0;
   if (f.expiry || !e_ok || r.push_mode == 1 || blind)
@@ -257,6 +271,8 @@ struct DecayFacts {
                                  // that round runs its own schedule
   bool pull_ahead = false;       // the replies of an anti-entropy exchange arrive in a round from here
                                  // on (p2pg_set_anti_entropy): that round runs its own schedule
+  bool cut_ahead = false;        // a netsplit acts on a round from here on (p2pg_set_netsplit): that
+                                 // round runs its own schedule
   bool frontier_needed = false;  // every round's frontier rows are read whole (lost count, tallies,
                                  // relay policy)
   bool autostop = true;
@@ -268,7 +284,7 @@ inline bool decay_batchable(const RoundHistory& h, const RoundRules& r, const Ro
                             const DecayFacts& f) {
   return f.round > 0 && !f.frontier_needed && c.gossip && h.saw_dense && !h.last_push_e &&
          h.last_new < h.prev2_new && h.prev_sw > 0 && !f.consume_next && !f.arr_pending &&
-         !f.late_starts && !f.expiry_ahead && !f.offline_ahead && !f.pull_ahead && !c.partitioned && f.autostop && r.push_mode != 2 &&
+         !f.late_starts && !f.expiry_ahead && !f.offline_ahead && !f.pull_ahead && !f.cut_ahead && !c.partitioned && f.autostop && r.push_mode != 2 &&
          !f.auto_buf && c.sparse_scatter &&
          h.last_new * 16 < (uint64_t)f.V;  // the tail: small rounds, where the syncs dominate
 }

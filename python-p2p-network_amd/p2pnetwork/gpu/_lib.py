@@ -100,6 +100,7 @@ SIGNATURES = {
     "p2pg_churn_lost": (ctypes.c_int, [_U32, _U32, _U32, _U32, _U64]),
     "p2pg_relay_muted": (ctypes.c_int, [_U32, _U32, _U32, _U32, _U64]),
     "p2pg_peer_offline": (ctypes.c_int, [_I32, _I32, _I32]),
+    "p2pg_link_cut": (ctypes.c_int, [_I32, _I32, _I32, _I32, _I32]),
     "p2pg_pull_partner_slot": (_I32, [_U32, _U32, _U32, _U64]),
     "p2pg_create": (ctypes.c_int, [ctypes.POINTER(Config), _PP]),
     "p2pg_load_csr": (ctypes.c_int, [_P, _I64, _P, _P]),
@@ -109,6 +110,7 @@ SIGNATURES = {
     "p2pg_set_ttl": (ctypes.c_int, [_P, _I32, _P]),
     "p2pg_set_relay_policy": (ctypes.c_int, [_P, _I64, _P, _U64]),
     "p2pg_set_downtime": (ctypes.c_int, [_P, _I64, _P, _P]),
+    "p2pg_set_netsplit": (ctypes.c_int, [_P, _I64, _P, _I32, _I32]),
     "p2pg_set_anti_entropy": (ctypes.c_int, [_P, _I32, _I32, _I32, _U64]),
     "p2pg_get_pull_stats": (ctypes.c_int, [_P, _I64, _P, ctypes.POINTER(_I64)]),
     "p2pg_reset": (ctypes.c_int, [_P]),

@@ -200,6 +200,7 @@ class GraphNetwork:
         self.offline_from = None     # int32 [V]: the peers' downtime intervals [from, until)
         self.offline_until = None    # (None = no downtime; until 0x7FFFFFFF = forever)
         self.anti_entropy = None     # (period, first_round, last_round, seed), None = not set
+        self.netsplit = None         # (side int32 [V], cut_from, cut_until), None = not set
         self._autostop = bool(autostop)
         self._next_round = 0         # the next round the engine runs
         self._quiet = False          # the engine went quiet (further steps run no round)
@@ -379,6 +380,40 @@ class GraphNetwork:
         on = bool((f >= 0).any())
         self.offline_from = f if on else None
         self.offline_until = u if on else None
+
+    @staticmethod
+    def link_cut(round, side_a, side_b, cut_from, cut_until):
+        """Is a connection between a peer of ``side_a`` and a peer of ``side_b`` cut in ``round``
+        under the window [``cut_from``, ``cut_until``)?  (p2pg_link_cut)"""
+        return bool(_lib.lib().p2pg_link_cut(int(round), int(side_a), int(side_b), int(cut_from), int(cut_until)))
+
+    def set_netsplit(self, side, cut_from=0, cut_until=0):
+        """A network partition that heals, before round 0 runs (or after ``reset``): peer v is on
+        side ``side[v]`` (>= 0) and every connection between two sides is cut in the rounds
+        ``cut_from <= r < cut_until``.  Peers keep their connections and go on sending over a cut
+        connection; a send that would arrive in a cut round is counted by its sender and lost,
+        anti-entropy requests and replies included.  ``set_netsplit(None)``, equal sides or an empty
+        window remove it.  Not together with hop limits, a relay policy, ``drop_relays``,
+        ``update_edges`` or snapshots.  ``reset`` and ``broadcast`` keep it (p2pg_set_netsplit)."""
+        V = self.graph.V
+        if side is None:
+            self._check(_lib.lib().p2pg_set_netsplit(self._h, V, None, 0, 0))
+            self.netsplit = None
+            return
+        s = np.array(side, dtype=np.int64, ndmin=1)
+        if s.shape != (V,):
+            raise ValueError("side must hold one side per peer")
+        for x in (cut_from, cut_until):
+            if not -(1 << 31) <= int(x) <= _FOREVER:
+                raise ValueError("cut_from and cut_until must be int32 rounds")
+        if ((s < -(1 << 31)) | (s > _FOREVER)).any():
+            raise ValueError("sides must be int32")
+        s = np.ascontiguousarray(s, dtype=np.int32)
+        self._check(_lib.lib().p2pg_set_netsplit(self._h, V, _lib.ptr(s), int(cut_from), int(cut_until)))
+        g = self.graph
+        crossing = bool((s[np.repeat(np.arange(V), np.diff(g.rowptr))] != s[g.colidx]).any())
+        on = crossing and int(cut_from) < int(cut_until)
+        self.netsplit = (s, int(cut_from), int(cut_until)) if on else None
 
     def set_anti_entropy(self, period, first_round=0, last_round=None, seed=0):
         """Periodic pull repair, before round 0 runs (or after ``reset``): in every round r with
